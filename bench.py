@@ -9,12 +9,22 @@ HBM.
   --scaling strong (default) 1 GiB in total (256 blocks) dealt over the N GPUs: config 4 as
                    BASELINE writes it ("1 GiB ... round-robin over 1->2->4->8 GPUs").
   --scaling weak   1 GiB per GPU: rank r owns blocks r, r+N, r+2N, ... of the N GiB stream.
-value = input bytes of all ranks x steps / max-over-ranks time. At N > 1 the strong line also
-carries `weak_scaling`: the same legs timed with 1 GiB per GPU (the per-GPU batch of N = 1).
+value = input bytes of all ranks x steps / max-over-ranks time. At N > 1 the strong line of
+a `--full` run also carries `weak_scaling`: the same legs timed with 1 GiB per GPU (the per-GPU
+batch of N = 1).
 
 `value` is the device-resident rate (inputs already in HBM, records left in HBM) that the
 driver's bench contract asks for. It is NOT SURVEY §8(d)'s graded figure: that is
-`pcie_inclusive` below, the number README quotes first. The line carries:
+`pcie_inclusive` below, the number README quotes first.
+
+A plain run does only what `value` needs: it generates the inputs, warms up, times the K
+steps and prints the line (metric, value, ms_per_step, ratio, config). `--dump-outputs DIR`
+then also writes what the last timed step computed (dump_outputs below). Everything else
+runs only with `--full`, after the timed steps, and adds to the line:
+  weak_scaling    N > 1, --scaling strong: the same legs with 1 GiB per GPU.
+  parity          every record against the reference manifest.
+  kernels_ms_per_step, host_wall_ms_per_step   a one-stream pass with HIP events per launch.
+  decode          GPU decode of the same records, round trip checked.
   pcie_inclusive  SURVEY §8(d)'s graded t_encode: the same blocks streamed by bmh_compress_host
                   from page-locked host memory (first H2D) to the records in page-locked host
                   memory (last D2H), and its graded roofline fraction.
@@ -23,7 +33,8 @@ driver's bench contract asks for. It is NOT SURVEY §8(d)'s graded figure: that 
   cpu_baseline    the reference itself (oracle/_ref/ref_COMPRESS, compiled from its sources)
                   on every host core of the box, one 4 MiB block per process; plus Calgary.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--full]
+                  [--dump-outputs DIR]
   torchrun --nproc-per-node N bench.py --gpus N ...     (one process per GPU)
 
 Prints ONE JSON line on rank 0 (plus diagnostics on stderr).
@@ -39,6 +50,7 @@ import subprocess
 import sys
 import tempfile
 import time
+import zlib
 
 import numpy as np
 
@@ -144,6 +156,30 @@ class DeviceEncoder:
             return []
         a = self.d_out.download(int(self.ro[-1])).tobytes()
         return [a[int(self.ro[i]):int(self.ro[i + 1])] for i in range(len(self.mine))]
+
+
+DUMP_SAMPLE = 1 << 23  # record bytes kept by --dump-outputs (float32: 32 MiB)
+
+
+def dump_outputs(r: dist.Rank, enc: DeviceEncoder, out_dir: str) -> None:
+    """What the last timed step handed its caller, as .npy files for an output-for-output
+    comparison of two builds (the inputs are a fixed stream, so the files are too):
+      record_offsets  float64, the nblk + 1 offsets bmh_encode_blocks_dev returned (exact: < 2^53)
+      record_crc32    float64, CRC-32 of every whole record (covers every output byte)
+      record_bytes    float32, the records' bytes; beyond DUMP_SAMPLE bytes a fixed sample of
+                      them (DUMP_SAMPLE positions in [0, total) drawn by default_rng(0), sorted).
+    At N > 1 every rank writes its own files, suffixed _rank<r>."""
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f"_rank{r.rank}" if r.world > 1 else ""
+    ro = np.asarray(enc.ro, dtype=np.uint64)
+    total = int(ro[-1])
+    raw = enc.d_out.download(total) if total else np.zeros(0, np.uint8)
+    crc = [zlib.crc32(raw[int(ro[i]):int(ro[i + 1])]) for i in range(len(ro) - 1)]
+    if total > DUMP_SAMPLE:
+        raw = raw[np.sort(np.random.default_rng(0).integers(0, total, DUMP_SAMPLE))]
+    np.save(os.path.join(out_dir, f"record_offsets{sfx}.npy"), ro.astype(np.float64))
+    np.save(os.path.join(out_dir, f"record_crc32{sfx}.npy"), np.asarray(crc, dtype=np.float64))
+    np.save(os.path.join(out_dir, f"record_bytes{sfx}.npy"), raw.astype(np.float32))
 
 
 def kernel_leg(enc: DeviceEncoder, ksteps: int) -> tuple[dict, dict]:
@@ -373,7 +409,14 @@ def main() -> None:
                     help="pipelines (streams) per device batch for every leg (0: the library's rule; experiments)")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE",
                     help="bmh_ctx_set_option for experiments (bmh.Context.OPTIONS), e.g. mtf_chunk=2048")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the weak-scaling, per-kernel, parity, decode, Calgary, "
+                         "PCIe-inclusive and CPU-baseline legs (the options above size them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (see dump_outputs)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # control plane over gloo (barriers + scalar reductions only, bmh/dist.py); ranks map to
     # devices local_rank mod device_count, so N ranks can also be rehearsed on fewer GPUs
@@ -394,6 +437,42 @@ def main() -> None:
 
     res = encode_leg(r, enc, a.steps, a.warmup)
     timed_pipes = enc.pipelines  # pipelines the timed steps ran on (before the 1-stream kernel pass)
+    if a.dump_outputs:
+        dump_outputs(r, enc, a.dump_outputs)
+
+    line = None
+    if r.rank == 0:
+        steps, dt = a.steps, res["dt"]
+        value = res["in_bytes"] * steps / dt / 1e6
+        wl = ("BASELINE config 4: 1 GiB uniform-random bytes per GPU, 4 MiB blocks, round-robin block deal"
+              if a.scaling == "weak" else
+              f"BASELINE config 4: {a.total_bytes >> 20} MiB uniform-random bytes in total, 4 MiB blocks dealt "
+              f"round-robin over {world} GPU(s)")
+        line = {
+            "metric": METRIC, "value": round(value, 2), "unit": "MB/s", "n_gpus": world, "steps": steps,
+            "warmup": a.warmup, "ms_per_step": round(dt / steps * 1e3, 3), "higher_is_better": True,
+            "scaling": a.scaling, "vs_baseline": None, "dtype": "u8",
+            "data": "synthetic: splitmix64(seed 0) bytes (SURVEY App. D), generated in HBM",
+            "config": {"workload": wl, "block_size": bs, "blocks_per_gpu": len(mine),
+                       "bytes_per_gpu": enc.in_bytes, "parallelism": f"{world} independent GPU(s), no collective",
+                       "streams_per_gpu": timed_pipes},
+            "ratio": round(res["out_bytes"] / res["in_bytes"], 7),
+            "device_only_graded_frac": round(value / 1e3 / (world * HBM_PEAK_GBS), 6),
+        }
+    if a.full:
+        more = full_legs(a, r, ctx, enc, mine)
+        if r.rank == 0:
+            line.update(more)
+    if r.rank == 0:
+        print(json.dumps(line), flush=True)
+    ctx.close()
+    dist.finalize(r)
+
+
+def full_legs(a, r: dist.Rank, ctx: bmh.Context, enc: DeviceEncoder, mine: list[int]) -> dict:
+    """--full: every leg beyond the headline figure, run after the timed steps; returns the
+    keys they add to the line (meaningful on rank 0)."""
+    world, bs = r.world, a.block_size
     weak = None
     wsteps = a.steps if a.weak_steps < 0 else a.weak_steps
     if a.scaling == "strong" and world > 1 and wsteps > 0:
@@ -446,39 +525,23 @@ def main() -> None:
     sb = next((int(o.split("=", 1)[1]) for o in a.opt if o.split("=", 1)[0] == "stream_batch"), 0)
     pcie = pcie_leg(r, enc, a.pcie_steps, 1, sb) if a.pcie_steps > 0 else None
 
-    if r.rank == 0:
-        steps, dt = a.steps, res["dt"]
-        value = res["in_bytes"] * steps / dt / 1e6
-        wl = ("BASELINE config 4: 1 GiB uniform-random bytes per GPU, 4 MiB blocks, round-robin block deal"
-              if a.scaling == "weak" else
-              f"BASELINE config 4: {a.total_bytes >> 20} MiB uniform-random bytes in total, 4 MiB blocks dealt "
-              f"round-robin over {world} GPU(s)")
-        line = {
-            "metric": METRIC, "value": round(value, 2), "unit": "MB/s", "n_gpus": world, "steps": steps,
-            "warmup": a.warmup, "ms_per_step": round(dt / steps * 1e3, 3), "higher_is_better": True,
-            "scaling": a.scaling, "vs_baseline": None, "dtype": "u8",
-            "data": "synthetic: splitmix64(seed 0) bytes (SURVEY App. D), generated in HBM",
-            "config": {"workload": wl, "block_size": bs, "blocks_per_gpu": len(mine),
-                       "bytes_per_gpu": enc.in_bytes, "parallelism": f"{world} independent GPU(s), no collective",
-                       "streams_per_gpu": timed_pipes},
-            "ratio": round(res["out_bytes"] / res["in_bytes"], 7),
-            "device_only_graded_frac": round(value / 1e3 / (world * HBM_PEAK_GBS), 6),
-            "weak_scaling": weak,
-            "pcie_inclusive": pcie,
-            "calgary": cal,
-            "roofline": roofline(stats, ksteps, enc.in_bytes),
-            "kernels_ms_per_step": {k: round(v[1] / ksteps, 3) for k, v in sorted(stats.items(), key=lambda kv: -kv[1][1])},
-            "kernel_pass": "one stream (BMH_OPT_ONE_PIPELINE: the timed path's dense / speculative decisions kept)",
-            "host_wall_ms_per_step": {k: round(v[1] / ksteps, 3) for k, v in walls.items()},
-            "parity": parity,
-            "decode": dec,
-        }
-        # rank 0 times the reference CPU path after every timed leg, at any world size (the
-        # other ranks have left their legs: nothing else runs on the box's cores or GPUs)
-        line["cpu_baseline"] = None if a.no_cpu_baseline else cpu_baseline(bs, a.cpu_procs or None)
-        print(json.dumps(line), flush=True)
-    ctx.close()
-    dist.finalize(r)
+    if r.rank != 0:
+        return {}
+    more = {
+        "weak_scaling": weak,
+        "pcie_inclusive": pcie,
+        "calgary": cal,
+        "roofline": roofline(stats, ksteps, enc.in_bytes),
+        "kernels_ms_per_step": {k: round(v[1] / ksteps, 3) for k, v in sorted(stats.items(), key=lambda kv: -kv[1][1])},
+        "kernel_pass": "one stream (BMH_OPT_ONE_PIPELINE: the timed path's dense / speculative decisions kept)",
+        "host_wall_ms_per_step": {k: round(v[1] / ksteps, 3) for k, v in walls.items()},
+        "parity": parity,
+        "decode": dec,
+    }
+    # rank 0 times the reference CPU path after every timed leg, at any world size (the
+    # other ranks have left their legs: nothing else runs on the box's cores or GPUs)
+    more["cpu_baseline"] = None if a.no_cpu_baseline else cpu_baseline(bs, a.cpu_procs or None)
+    return more
 
 
 if __name__ == "__main__":

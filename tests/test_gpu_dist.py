@@ -34,7 +34,7 @@ def test_world2_bench_on_gpu(scaling):
     env = dict(os.environ)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"),
-           "--gpus", "2", "--steps", "2", "--warmup", "1", "--scaling", scaling, "--cpu-procs", "2"]
+           "--gpus", "2", "--steps", "2", "--warmup", "1", "--scaling", scaling, "--cpu-procs", "2", "--full"]
     if scaling == "weak":  # 64 blocks per rank, every leg of the default line
         cmd += ["--bytes-per-gpu", str(256 << 20), "--decode-steps", "1", "--pcie-steps", "1", "--calgary-steps", "1"]
     else:  # config 4 as written (1 GiB dealt over the ranks) + the 1 GiB-per-GPU leg, here 256 MiB

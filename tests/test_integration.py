@@ -6,7 +6,7 @@ its 3-argument print_metrics (main.cpp:294-298), linked with libbmh.so.
 CPU (needs /root/reference, i.e. the build container): the file compiles and links as written;
 the wrong-argument contract of main.cpp:440-443 holds; compress() and decompress() both fail
 loudly without a GPU (decompress() decodes on the GPU since round 6).
-GPU: the binary built here (integration/_build, travels with the snapshot) compresses every
+GPU: the binary build() made (oracle/_ref, else integration/_build) compresses every
 Calgary file to the reference's record and prints the reference's stdout line, and its
 decompress() decodes every golden Calgary record on the GPU back to the file."""
 import json
@@ -20,7 +20,11 @@ from oracle_ffi import CALGARY, GOLDEN, golden_calgary
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_DIR = "/root/reference"
-BUILT = os.path.join(REPO, "integration", "_build", "bmh_ref_compress")
+# build() leaves the binding beside the reference's binaries in oracle/_ref (what a host without
+# the reference keeps from the build) and in integration/_build
+BUILT = next((p for p in (os.path.join(REPO, "oracle", "_ref", "bmh_ref_compress"),
+                          os.path.join(REPO, "integration", "_build", "bmh_ref_compress")) if os.path.exists(p)),
+             os.path.join(REPO, "integration", "_build", "bmh_ref_compress"))
 LIB = os.path.join(REPO, "bwt-mtf-huffman-compressor_amd", "lib", "libbmh.so")
 
 

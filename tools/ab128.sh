@@ -6,7 +6,7 @@ for r in $(seq $rounds); do
   for l in "$@"; do
     lib=$l; [ "$l" = "." ] && lib=bwt-mtf-huffman-compressor_amd/lib/libbmh.so
     n=$(echo $l | tr '/.' '__')
-    BMH_LIB=$lib timeout -k 10 120 python3 bench.py --steps 40 --warmup 5 --no-cpu-baseline --decode-steps 0 --pcie-steps 0 --calgary-steps 0 --total-bytes 134217728 > $o/${n}_$r.json 2>/dev/null || exit 1
+    BMH_LIB=$lib timeout -k 10 120 python3 bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --decode-steps 0 --pcie-steps 0 --calgary-steps 0 --total-bytes 134217728 > $o/${n}_$r.json 2>/dev/null || exit 1
     python3 -c "import json; d=json.loads(open('$o/${n}_$r.json').read().strip().splitlines()[-1]); print('$l'.ljust(28), d['ms_per_step'], d['parity'][:6])"
   done
 done

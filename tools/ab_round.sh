@@ -11,7 +11,7 @@ for r in $(seq $rounds); do
   i=0
   for cfg in "$@"; do
     i=$((i+1))
-    timeout -k 10 200 python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --decode-steps 0 --pcie-steps 2 --calgary-steps 3 $cfg \
+    timeout -k 10 200 python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --decode-steps 0 --pcie-steps 2 --calgary-steps 3 $cfg \
       > $o/b${r}_$i.json 2> $o/b${r}_$i.err || exit $?
     python3 -c "import json,sys; d=json.loads(open('$o/b${r}_$i.json').read().strip().splitlines()[-1]); k=d['kernels_ms_per_step']; print(f\"[{sys.argv[1]:28s}] {d['value']:9.1f} MB/s {d['ms_per_step']:7.3f} ms pcie {d['pcie_inclusive']['ms_per_step']:6.2f} cal {d['calgary']['whole_files']['ms']:.2f}/{d['calgary']['blocks_256k']['ms']:.2f} {d['parity'][:7]}\", {a: k[a] for a in list(k)[:6]})" "$cfg"
   done

@@ -7,7 +7,7 @@ set -e
 export TMPDIR=/tmp
 o=gpurun_out/prof
 mkdir -p $o
-timeout -k 10 400 python3 bench.py > $o/bench.json 2> $o/bench.err
+timeout -k 10 400 python3 bench.py --full > $o/bench.json 2> $o/bench.err
 # one stream, like bench.py's per-kernel pass, so the per-kernel durations agree with its roofline
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $o/stats -o run --output-format csv -- \
     python3 bench.py --pipelines 1 --steps 5 --warmup 1 --no-cpu-baseline --decode-steps 0 --pcie-steps 0 --calgary-steps 0 > $o/stats_bench.json 2> $o/stats.err

@@ -22,7 +22,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def run(total: int, steps: int, pcie_steps: int) -> dict:
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", str(steps), "--warmup", "3",
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--full", "--steps", str(steps), "--warmup", "3",
            "--total-bytes", str(total), "--no-cpu-baseline", "--decode-steps", "0",
            "--pcie-steps", str(pcie_steps), "--calgary-steps", "0"]
     r = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=300)

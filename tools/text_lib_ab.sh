@@ -11,7 +11,7 @@ for r in 1 2; do
     for cfg in "100 1" "128 16" "128 4"; do
       BMH_LIB=$lib timeout -k 10 150 python3 tools/text_bench.py $cfg > $o/${n}_t${cfg// /_}_$r.json || exit 1
     done
-    BMH_LIB=$lib timeout -k 10 200 python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --decode-steps 0 --pcie-steps 0 --calgary-steps 0 > $o/${n}_b_$r.json 2>/dev/null || exit 1
+    BMH_LIB=$lib timeout -k 10 200 python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --decode-steps 0 --pcie-steps 0 --calgary-steps 0 > $o/${n}_b_$r.json 2>/dev/null || exit 1
     python3 - $o $n $r $l <<'P'
 import json, sys
 o, n, r, l = sys.argv[1:]

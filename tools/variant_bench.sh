@@ -6,10 +6,10 @@ set -e
 export TMPDIR=/tmp
 o=gpurun_out/variants
 mkdir -p $o
-timeout -k 10 200 python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --decode-steps 0 --pcie-steps 0 --calgary-steps 0 > $o/base.json 2> $o/base.err
+timeout -k 10 200 python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --decode-steps 0 --pcie-steps 0 --calgary-steps 0 > $o/base.json 2> $o/base.err
 names=${@:-$(ls variants)}
 for n in $names; do
-    BMH_LIB=variants/$n/libbmh.so timeout -k 10 200 python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline \
+    BMH_LIB=variants/$n/libbmh.so timeout -k 10 200 python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline \
         --decode-steps 0 --pcie-steps 0 --calgary-steps 0 > $o/$n.json 2> $o/$n.err
 done
 python3 - <<'EOF'
