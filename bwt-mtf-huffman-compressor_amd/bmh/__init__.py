@@ -98,6 +98,12 @@ _SIGS = {
     "bmh_synth_splitmix64_dev": (C.c_int, [P, P, U64, U64, U64]),
     "bmh_synth_zipf_dev": (C.c_int, [P, P, U64, U64]),
     "bmh_check_violations": (C.c_int64, [P, U32]),
+    "bmh_crc32_dev": (C.c_int, [P, P, PU64, U32, C.POINTER(U32)]),
+    "bmh_crc32_host": (U32, [U32, P, U64]),
+    "bmh_compress_bound_checked": (U64, [U64, U64]),
+    "bmh_verify_dev": (C.c_int, [P, P, U64, PU64, PU64]),
+    "bmh_container_version": (C.c_int, [P, U64]),
+    "bmh_container_crc32": (C.c_int, [P, U64, U64, C.POINTER(U32)]),
 }
 
 
@@ -260,7 +266,7 @@ class Context:
 
     # ---- tuning options (include/bmh.h BMH_OPT_*; 0 restores the library's rule)
     OPTIONS = {"pipelines": 1, "stream_batch": 2, "max_batch": 3, "mtf_chunk": 4, "check_lists": 5, "one_pipeline": 6,
-               "copy_threads": 7}
+               "copy_threads": 7, "checksum": 8}
 
     def set_option(self, name: str, value: int) -> None:
         _check(lib().bmh_ctx_set_option(self.h, self.OPTIONS[name], int(value)), f"set_option({name})")
@@ -317,6 +323,14 @@ class Context:
                                            _u64p(ro)), "encode_blocks")
         return ro
 
+    def crc32_dev(self, d_in, offs: np.ndarray) -> np.ndarray:
+        """CRC-32 (zlib's) of every block of a batch in device memory, computed on the GPU."""
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        crc = np.zeros(len(offs) - 1, dtype=np.uint32)
+        _check(lib().bmh_crc32_dev(self.h, _dp(d_in), _u64p(offs), len(offs) - 1, crc.ctypes.data_as(C.POINTER(U32))),
+               "crc32")
+        return crc
+
     def decode_blocks_dev(self, d_rec, rec_offs: np.ndarray, d_out, out_cap: int) -> np.ndarray:
         """GPU decode of records in device memory; returns the output offsets (nblocks+1)."""
         rec_offs = np.ascontiguousarray(rec_offs, dtype=np.uint64)
@@ -333,6 +347,20 @@ class Context:
         out = np.empty(max(n.value, 1), dtype=np.uint8)
         _check(lib().bmh_decompress_dev(self.h, _ptr(a), a.size, _ptr(out), n.value, C.byref(n)), "decompress_dev")
         return out[: n.value].tobytes()
+
+    def verify(self, data) -> int:
+        """Decodes a record or container on this GPU without returning the bytes and checks the
+        CRC-32 of every block of a version-2 container there; returns the decoded size. Raises
+        BmhError, whose `bad_block` is the first block with a wrong CRC (None: structural)."""
+        a = as_u8(data)
+        n, bad = C.c_uint64(), C.c_uint64()
+        st = lib().bmh_verify_dev(self.h, _ptr(a), a.size, C.byref(n), C.byref(bad))
+        try:
+            _check(st, "verify_dev")
+        except BmhError as e:
+            e.bad_block = None if bad.value == 2**64 - 1 else bad.value
+            raise
+        return n.value
 
     def synth_splitmix64(self, d_out, nbytes: int, seed: int = 0, offset: int = 0) -> None:
         _check(lib().bmh_synth_splitmix64_dev(self.h, _dp(d_out), nbytes, seed, offset), "synth")
@@ -359,14 +387,10 @@ class Context:
             d_out.free()
         return [raw[int(ro[i]):int(ro[i + 1])].tobytes() for i in range(len(arrs))]
 
-    def compress_bytes(self, data, block_size: int = 0) -> bytes:
-        a = as_u8(data)
-        cap = int(lib().bmh_compress_bound(a.size, block_size))
-        out = np.empty(max(cap, 1), dtype=np.uint8)
-        olen = C.c_uint64()
-        _check(lib().bmh_compress_host(self.h, _ptr(a), a.size, block_size, _ptr(out), cap, C.byref(olen)),
-               "compress")
-        return out[: olen.value].tobytes()
+    def compress_bytes(self, data, block_size: int = 0, checksum: bool = False) -> bytes:
+        """bmh_compress_host; checksum=True writes a version-2 container with the CRC-32 of every
+        block (BMH_OPT_CHECKSUM for this call only: the option is 0 again afterwards)."""
+        return compress_bytes_multi([self], data, block_size, checksum)
 
 
 def _dp(x) -> C.c_void_p:
@@ -379,14 +403,21 @@ def _dp(x) -> C.c_void_p:
     return x
 
 
-def compress_bytes_multi(ctxs: Sequence[Context], data, block_size: int) -> bytes:
+def compress_bytes_multi(ctxs: Sequence[Context], data, block_size: int, checksum: bool = False) -> bytes:
     a = as_u8(data)
-    cap = int(lib().bmh_compress_bound(a.size, block_size))
+    L = lib()
+    cap = int((L.bmh_compress_bound_checked if checksum else L.bmh_compress_bound)(a.size, block_size))
     out = np.empty(max(cap, 1), dtype=np.uint8)
     olen = C.c_uint64()
     arr = (C.c_void_p * len(ctxs))(*[c.h.value for c in ctxs])
-    _check(lib().bmh_compress_host_multi(arr, len(ctxs), _ptr(a), a.size, block_size, _ptr(out), cap,
-                                         C.byref(olen)), "compress_multi")
+    if checksum:  # the option of ctxs[0] decides (include/bmh.h)
+        ctxs[0].set_option("checksum", 1)
+    try:
+        _check(L.bmh_compress_host_multi(arr, len(ctxs), _ptr(a), a.size, block_size, _ptr(out), cap,
+                                         C.byref(olen)), "compress_multi" if len(ctxs) > 1 else "compress")
+    finally:
+        if checksum:
+            ctxs[0].set_option("checksum", 0)
     return out[: olen.value].tobytes()
 
 
@@ -454,6 +485,31 @@ def container_records(data) -> list[bytes]:
 def is_container(data) -> bool:
     a = as_u8(data)
     return bool(lib().bmh_is_container(_ptr(a), a.size))
+
+
+def container_version(data) -> int:
+    """0: not a container (a bare record); 1; or 2 (with a CRC-32 per block)."""
+    a = as_u8(data)
+    return int(lib().bmh_container_version(_ptr(a), a.size))
+
+
+def container_crcs(data) -> list[int]:
+    """The stored CRC-32 of every block of a version-2 container."""
+    a = as_u8(data)
+    nb = C.c_uint64()
+    _check(lib().bmh_container_info(_ptr(a), a.size, C.byref(nb), None), "container_info")
+    out = []
+    for b in range(nb.value):
+        v = U32()
+        _check(lib().bmh_container_crc32(_ptr(a), a.size, b, C.byref(v)), "container_crc32")
+        out.append(v.value)
+    return out
+
+
+def crc32(data, crc: int = 0) -> int:
+    """zlib.crc32 semantics (bmh_crc32_host): the CRC the version-2 container stores."""
+    a = as_u8(data)
+    return int(lib().bmh_crc32_host(crc, _ptr(a), a.size))
 
 
 # ------------------------------------------------------- reference-named stage functions
@@ -570,4 +626,4 @@ def decompress(encoded_file_name: str, decoded_file_name: str) -> None:
 __all__ = ["BmhError", "CodeTable", "Context", "DevBuf", "lib", "bwt", "move_to_front", "huffman",
            "tree_to_bytes", "compress", "decompress", "compress_bytes_multi", "decompress_bytes",
            "record_to_mtf", "huffman_build", "node_ranks", "payload_bytes", "container_records", "is_container",
-           "metrics_line", "default_context"]
+           "container_version", "container_crcs", "crc32", "metrics_line", "default_context"]

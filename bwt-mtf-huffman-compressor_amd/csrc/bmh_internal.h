@@ -53,7 +53,8 @@ enum Slot : int {
     WS_CHIST, WS_BSTART, WS_COUNTERS, WS_LTILES, WS_LTHIST, WS_LSEGS, WS_SEGOR, WS_COOP, WS_LISTS, WS_L, WS_MTF,
     WS_MTF_R, WS_MTF_S, WS_MTF_SUPER, WS_MTF_CHUNKS, WS_FREQ, WS_FIRST, WS_PRIMARY, WS_PACK_BITS,
     WS_PACK_CHUNKS, WS_TABLES, WS_HDR, WS_HDR_OFFS, WS_IN, WS_OUT, WS_IN2, WS_OUT2, WS_IN3, WS_OUT3, WS_RESOLVED, WS_FIN_CUR, WS_FIN_NXT,
-    WS_DSEG_CUR, WS_DSEG_NXT, WS_DLARGE, WS_DLARGE2, WS_DGROUPS, WS_KEY8, WS_ROFFS, WS_STATUS, WS_PACK_HIST, WS_FINT_CUR, WS_FINT_NXT, WS_FINB_CUR, WS_FINB_NXT, WS_KEY8B, WS_RUN_MISC, WS_RUN_MOVE, WS_RUN_IN, WS_RUN_L, WS_RUNS, WS_RUN_PRIM, WS_BAND, WS_SYNTH, WS_ALPHA, WS_COUNT_
+    WS_DSEG_CUR, WS_DSEG_NXT, WS_DLARGE, WS_DLARGE2, WS_DGROUPS, WS_KEY8, WS_ROFFS, WS_STATUS, WS_PACK_HIST, WS_FINT_CUR, WS_FINT_NXT, WS_FINB_CUR, WS_FINB_NXT, WS_KEY8B, WS_RUN_MISC, WS_RUN_MOVE, WS_RUN_IN, WS_RUN_L, WS_RUNS, WS_RUN_PRIM, WS_BAND, WS_SYNTH, WS_ALPHA,
+    WS_CRC_TAB, WS_CRC_BLK, WS_CRC_PART, WS_CRC_OUT, WS_COUNT_
 };
 
 struct Ctx {
@@ -98,7 +99,7 @@ struct Ctx {
     // tuning options (bmh_ctx_set_option; 0 = the library's rule); sub-pipelines and the side
     // context copy their parent's at every call
     struct Options {
-        uint64_t pipelines = 0, stream_batch = 0, max_batch = 0, mtf_chunk = 0, check_lists = 0, one_pipeline = 0, copy_threads = 0;
+        uint64_t pipelines = 0, stream_batch = 0, max_batch = 0, mtf_chunk = 0, check_lists = 0, one_pipeline = 0, copy_threads = 0, checksum = 0;
     } opt;
     uint32_t last_pipelines = 0;  // pipelines of the last device batch encode (encode_blocks)
     uint64_t zipf_resume_tok0 = 0, zipf_resume_base = 0;  // synth_zipf: start of its last round
@@ -265,6 +266,27 @@ void pack_batch_dev(Ctx *c, const uint8_t *d_mtf, const Batch &bt, const DevTabl
 void histogram_batch(Ctx *c, const uint8_t *d_in, const Batch &bt, uint32_t *h_freq32, uint32_t *h_first32);
 void synth_splitmix64(Ctx *c, uint8_t *d_out, uint64_t nbytes, uint64_t seed, uint64_t offset);  // synth.hip
 void synth_zipf(Ctx *c, uint8_t *d_out, uint64_t nbytes, uint64_t offset);
+// CRC-32 (zlib / IEEE 802.3) of every block of a batch, one per block at d_crc (crc32.hip);
+// asynchronous on the context's stream.
+void crc32_batch(Ctx *c, const uint8_t *d_in, const Batch &bt, uint32_t *d_crc);
+
+// CRC-32 arithmetic shared by the host code and the kernels. A CRC register is a polynomial
+// over GF(2) modulo P, reflected: bit 31 is x^0, bit 0 is x^31.
+constexpr uint32_t kCrcPoly = 0xEDB88320u;
+// a * b mod P
+__host__ __device__ inline uint32_t crc32_mul(uint32_t a, uint32_t b)
+{
+    uint32_t p = 0;
+    for (int i = 0; i < 32; ++i) {
+        p ^= (0u - (a >> 31)) & b;
+        a <<= 1;
+        b = (b >> 1) ^ ((0u - (b & 1u)) & kCrcPoly);
+    }
+    return p;
+}
+uint32_t crc32_xpow8(uint64_t nbytes);  // x^(8 * nbytes) mod P: multiplying by it appends nbytes zero bytes (record.cpp)
+const uint32_t *crc32_table0();         // the byte-at-a-time table (256 entries)
+uint32_t crc32_host(uint32_t crc, const uint8_t *p, uint64_t n);  // zlib semantics, slice-by-8
 
 // Host Huffman (huffman_host.cpp). n = the block's size: below kBandCeil the tie-break follows
 // the reference's heap history (heap_order.cpp); n = 0 takes the closed-form order.
@@ -307,16 +329,25 @@ void decode_blocks(Ctx *c, const uint8_t *d_rec, const uint64_t *rec_offs, uint3
 constexpr uint64_t kRecordHeader = 24;
 void put_u64(uint8_t *p, uint64_t v);
 uint64_t get_u64(const uint8_t *p);
-extern const uint8_t kContainerMagic[8];
+extern const uint8_t kContainerMagic[8], kContainerMagic2[8];
 uint64_t record_n(const uint8_t *rec, uint64_t len);
 void record_to_mtf(const uint8_t *rec, uint64_t len, uint8_t *mtf, uint64_t cap, uint64_t *n_out);
 void decode_record(const uint8_t *rec, uint64_t len, uint8_t *out, uint64_t cap, uint64_t *n_out);
 struct ContainerView {
     uint64_t block_size, nblocks, total;
     std::vector<uint64_t> rec_off, rec_len;
+    int version = 1;            // 2: with the CRC-32 of every block's plain bytes
+    std::vector<uint32_t> crc;  // version 2: nblocks entries
 };
 ContainerView parse_container(const uint8_t *in, uint64_t len);
 bool is_container(const uint8_t *in, uint64_t len);
+int container_version(const uint8_t *in, uint64_t len);  // 0: not a container
+// bytes before the first record: header, record lengths and, in version 2, the CRCs padded to 8
+inline uint64_t container_table_bytes(int version, uint64_t nblocks)
+{
+    return 32 + 8 * nblocks + (version == 2 ? (4 * nblocks + 7) / 8 * 8 : 0);
+}
+[[noreturn]] void fail_crc(uint64_t block, uint32_t stored, uint32_t computed);
 void decompress(const uint8_t *in, uint64_t len, uint8_t *out, uint64_t cap, uint64_t *n_out);
 
 }  // namespace bmh

@@ -638,8 +638,10 @@ struct RecRef {
 
 // Receives the records of consecutive entries [i0, i0 + cnt) of the block list: record j at
 // src + ro[j] .. src + ro[j + 1] (pinned staging, valid only during the call; or, with a
-// pinned destination, their final place).
-using RecordSink = std::function<void(size_t i0, size_t cnt, const uint8_t *src, const uint64_t *ro)>;
+// pinned destination, their final place). crc: the CRC-32 of each of those blocks' plain bytes
+// when the call asked for checksums, else nullptr.
+using RecordSink =
+    std::function<void(size_t i0, size_t cnt, const uint8_t *src, const uint64_t *ro, const uint32_t *crc)>;
 
 // Pinned fast path (the caller's buffers are page-locked): `in_pinned` issues the H2D copies
 // straight from the caller's input; a PinnedOut lets the D2H copies land the records at their
@@ -650,7 +652,8 @@ struct PinnedOut {
 };
 
 static void encode_host_blocks(Ctx *c, const uint8_t *in, uint64_t n, uint64_t bs, const std::vector<uint64_t> &blist,
-                               const RecordSink &sink, bool in_pinned = false, PinnedOut *pout = nullptr)
+                               const RecordSink &sink, bool in_pinned = false, PinnedOut *pout = nullptr,
+                               bool checksum = false)
 {
     struct B {
         std::vector<uint64_t> blocks, offs;
@@ -709,6 +712,7 @@ static void encode_host_blocks(Ctx *c, const uint8_t *in, uint64_t n, uint64_t b
     size_t d2h_issued = 0;
     bool abort_ = false;
     std::vector<std::vector<uint64_t>> ro(K);
+    std::vector<std::vector<uint32_t>> crc(K);  // checksum: per batch, one per block
     std::string err;
     bmh_status st = BMH_OK;
     auto wait_for = [&](auto pred) {
@@ -772,7 +776,8 @@ static void encode_host_blocks(Ctx *c, const uint8_t *in, uint64_t n, uint64_t b
             const int s = (int)(k % NS);
             if (!wait_for([&] { return d2h_issued > k; })) return;
             BMH_HIP(hipEventSynchronize(ev_d2h[s]));
-            sink(first[k], batches[k].blocks.size(), pout ? dst[k] : c->stage_out[s], ro[k].data());
+            sink(first[k], batches[k].blocks.size(), pout ? dst[k] : c->stage_out[s], ro[k].data(),
+                 checksum ? crc[k].data() : nullptr);
             bump(written);
         }
     }));
@@ -785,7 +790,19 @@ static void encode_host_blocks(Ctx *c, const uint8_t *in, uint64_t n, uint64_t b
             const B &bt = batches[k];
             Batch b = make_batch(bt.offs.data(), (uint32_t)bt.blocks.size());
             ro[k].resize(bt.blocks.size() + 1);
-            encode_blocks(c, d_in[s], b, d_out[s], bt.cap, ro[k].data(), 2);  // pipelines A, B (create_streams)
+            if (checksum) {  // of the plain bytes, ahead of the encode on the context's stream
+                crc[k].resize(b.nblocks);
+                uint32_t *d_crc = (uint32_t *)c->get(WS_CRC_OUT, (size_t)b.nblocks * 4);
+                crc32_batch(c, d_in[s], b, d_crc);
+                c->d2h(crc[k].data(), d_crc, (size_t)b.nblocks * 4);
+            }
+            try {
+                encode_blocks(c, d_in[s], b, d_out[s], bt.cap, ro[k].data(), 2);  // pipelines A, B (create_streams)
+                if (checksum) c->sync();  // the CRCs have landed (the encode may have run on sub-pipelines)
+            } catch (...) {
+                if (checksum) c->deferred.clear();  // crc[k] goes with this call: no later sync may write it
+                throw;
+            }
             bump(encoded);
             if (!wait_for([&] { return written + NS > k; })) return;  // the writer is done with stage_out[s]
             const uint64_t bytes = ro[k][bt.blocks.size()];
@@ -809,24 +826,37 @@ static void encode_host_blocks(Ctx *c, const uint8_t *in, uint64_t n, uint64_t b
     if (st != BMH_OK) fail(st, err);
 }
 
+// Version-2 container at `out`: the CRCs of blocks [b0, b0 + cnt) at their place in the table,
+// and the table's zero padding.
+static void put_crc_table(uint8_t *out, uint64_t nblocks, uint64_t b0, uint64_t cnt, const uint32_t *crc)
+{
+    uint8_t *t = out + 32 + 8 * nblocks;
+    for (uint64_t i = 0; i < cnt; ++i)
+        for (int k = 0; k < 4; ++k) t[4 * (b0 + i) + k] = (uint8_t)(crc[i] >> (8 * k));
+    for (uint64_t o = 32 + 12 * nblocks; o < container_table_bytes(2, nblocks); ++o) out[o] = 0;
+}
+
 static void assemble(uint64_t n, uint64_t bs, uint64_t nblocks, const std::vector<RecRef> &recs, uint8_t *out,
-                     uint64_t out_cap, uint64_t *out_len)
+                     uint64_t out_cap, uint64_t *out_len, const uint32_t *crcs = nullptr)
 {
     uint64_t total = 0;
-    if (nblocks == 1) {
+    const int version = crcs ? 2 : 1;
+    if (nblocks == 1 && !crcs) {
         total = recs[0].len;
         if (total > out_cap) fail(BMH_ERANGE, "compress: output capacity too small");
         par_memcpy(out, recs[0].p, total, copy_threads());
     } else {
-        total = 32 + 8 * nblocks;
+        const uint64_t table = container_table_bytes(version, nblocks);
+        total = table;
         for (auto &r : recs) total += r.len;
         if (total > out_cap) fail(BMH_ERANGE, "compress: output capacity too small");
-        memcpy(out, kContainerMagic, 8);
+        memcpy(out, crcs ? kContainerMagic2 : kContainerMagic, 8);
         put_u64(out + 8, bs);
         put_u64(out + 16, nblocks);
         put_u64(out + 24, n);
         std::vector<uint64_t> at(nblocks);
-        uint64_t o = 32 + 8 * nblocks;
+        uint64_t o = table;
+        if (crcs) put_crc_table(out, nblocks, 0, nblocks, crcs);
         for (uint64_t b = 0; b < nblocks; ++b) {
             put_u64(out + 32 + 8 * b, recs[b].len);
             at[b] = o;
@@ -1103,6 +1133,21 @@ bmh_status bmh_histogram_dev(bmh_ctx *c, const uint8_t *d_in, const uint64_t *of
     API_END
 }
 
+bmh_status bmh_crc32_dev(bmh_ctx *c, const uint8_t *d_in, const uint64_t *offs, uint32_t nblocks, uint32_t *h_crc)
+{
+    API_BEGIN
+    use_device(c);
+    if (!d_in || !h_crc) fail(BMH_EINVAL, "null argument");
+    Batch bt = make_batch(offs, nblocks);
+    uint32_t *d_crc = (uint32_t *)c->get(WS_CRC_OUT, (size_t)nblocks * 4);
+    crc32_batch(c, d_in, bt, d_crc);
+    c->d2h(h_crc, d_crc, (size_t)nblocks * 4);
+    c->sync();
+    API_END
+}
+
+uint32_t bmh_crc32_host(uint32_t crc, const uint8_t *p, uint64_t n) { return p && n ? crc32_host(crc, p, n) : crc; }
+
 bmh_status bmh_huffman_build(const uint64_t freq[256], const uint64_t first[256], bmh_code_table *out)
 {
     API_BEGIN
@@ -1180,6 +1225,12 @@ uint64_t bmh_compress_bound(uint64_t n, uint64_t bs)
     return 32 + 8 * nb + nb * (kRecordHeader + 320 + 16) + n;
 }
 
+uint64_t bmh_compress_bound_checked(uint64_t n, uint64_t bs)
+{
+    const uint64_t nb = (bs == 0 || bs >= n) ? 1 : (n + bs - 1) / bs;
+    return container_table_bytes(2, nb) + nb * (kRecordHeader + 320 + 16) + n;
+}
+
 bmh_status bmh_compress_host(bmh_ctx *c, const uint8_t *in, uint64_t n, uint64_t block_size, uint8_t *out,
                              uint64_t out_cap, uint64_t *out_len)
 {
@@ -1208,7 +1259,9 @@ bmh_status bmh_compress_host_multi(bmh_ctx **ctxs, uint32_t nctx, const uint8_t 
     std::vector<std::string> err(nctx);
     // one context: records go straight from the staging slots to their place in `out`
     const bool direct = nctx == 1;
-    const uint64_t table = nblocks == 1 ? 0 : 32 + 8 * nblocks;
+    const bool checksum = ctxs[0]->opt.checksum != 0;  // BMH_OPT_CHECKSUM: a version-2 container, always
+    const uint64_t table = checksum ? container_table_bytes(2, nblocks) : nblocks == 1 ? 0 : 32 + 8 * nblocks;
+    std::vector<uint32_t> crcs(checksum && !direct ? nblocks : 0);
     use_device(ctxs[0]);
     // the DMA-only paths, decided per context device (several contexts may sit on other GPUs)
     std::vector<char> in_pinned(nctx);
@@ -1232,27 +1285,30 @@ bmh_status bmh_compress_host_multi(bmh_ctx **ctxs, uint32_t nctx, const uint8_t 
                 PinnedOut po{out, out_cap, table};
                 encode_host_blocks(
                     ctxs[g], in, n, bs, bl,
-                    [&](size_t i0, size_t cnt, const uint8_t *src, const uint64_t *ro) {
+                    [&](size_t i0, size_t cnt, const uint8_t *src, const uint64_t *ro, const uint32_t *crc) {
                         const uint64_t bytes = ro[cnt];
                         if (at + bytes > out_cap) fail(BMH_ERANGE, "compress: output capacity too small");
                         if (src != out + at) par_memcpy(out + at, src, bytes, copy_threads(ctxs[g]));
                         for (size_t i = 0; i < cnt; ++i) {
                             if (table) put_u64(out + 32 + 8 * (i0 + i), ro[i + 1] - ro[i]);
                         }
+                        if (crc) put_crc_table(out, nblocks, i0, cnt, crc);
                         at += bytes;
                     },
-                    in_pinned[g] != 0, out_pinned ? &po : nullptr);
+                    in_pinned[g] != 0, out_pinned ? &po : nullptr, checksum);
             } else {
                 encode_host_blocks(ctxs[g], in, n, bs, bl,
-                                   [&](size_t i0, size_t cnt, const uint8_t *src, const uint64_t *ro) {
+                                   [&](size_t i0, size_t cnt, const uint8_t *src, const uint64_t *ro,
+                                       const uint32_t *crc) {
                                        const uint64_t bytes = ro[cnt];
                                        std::unique_ptr<uint8_t[]> buf(new uint8_t[std::max<uint64_t>(bytes, 1)]);
                                        par_memcpy(buf.get(), src, bytes, copy_threads(ctxs[g]));
                                        for (size_t i = 0; i < cnt; ++i)
                                            recs[bl[i0 + i]] = RecRef{buf.get() + ro[i], ro[i + 1] - ro[i]};
+                                       for (size_t i = 0; crc && i < cnt; ++i) crcs[bl[i0 + i]] = crc[i];
                                        store[g].push_back(std::move(buf));
                                    },
-                                   in_pinned[g] != 0);
+                                   in_pinned[g] != 0, nullptr, checksum);
             }
         } catch (const Error &e) {
             st[g] = e.status;
@@ -1276,14 +1332,14 @@ bmh_status bmh_compress_host_multi(bmh_ctx **ctxs, uint32_t nctx, const uint8_t 
         if (st[g] != BMH_OK) fail(st[g], err[g]);
     if (direct) {
         if (table) {
-            memcpy(out, kContainerMagic, 8);
+            memcpy(out, checksum ? kContainerMagic2 : kContainerMagic, 8);
             put_u64(out + 8, bs);
             put_u64(out + 16, nblocks);
             put_u64(out + 24, n);
         }
         *out_len = at;
     } else {
-        assemble(n, bs, nblocks, recs, out, out_cap, out_len);
+        assemble(n, bs, nblocks, recs, out, out_cap, out_len, checksum ? crcs.data() : nullptr);
     }
     API_END
 }
@@ -1306,17 +1362,19 @@ bmh_status bmh_decode_blocks_dev(bmh_ctx *c, const uint8_t *d_rec, const uint64_
     API_END
 }
 
-bmh_status bmh_decompress_dev(bmh_ctx *c, const uint8_t *in, uint64_t len, uint8_t *out, uint64_t cap, uint64_t *n_out)
+// bmh_decompress_dev, or with `verify` bmh_verify_dev: the same decode with no output buffer and
+// no D2H of the plain bytes. *bad receives the first block whose CRC-32 differs (version 2).
+static void decompress_dev(bmh_ctx *c, const uint8_t *in, uint64_t len, uint8_t *out, uint64_t cap, uint64_t *n_out,
+                           bool verify, uint64_t *bad)
 {
-    API_BEGIN
-    use_device(c);
-    if (!in || !n_out) fail(BMH_EINVAL, "null argument");
     // record list (a single record, or the records of a container)
     std::vector<uint64_t> ro, rl;
+    std::vector<uint32_t> want;  // version 2: the stored CRCs
     if (is_container(in, len)) {
         ContainerView v = parse_container(in, len);
         ro = v.rec_off;
         rl = v.rec_len;
+        want = v.crc;
     } else {
         ro.push_back(0);
         rl.push_back(len);
@@ -1328,8 +1386,11 @@ bmh_status bmh_decompress_dev(bmh_ctx *c, const uint8_t *in, uint64_t len, uint8
         total += ns[b];
     }
     *n_out = total;
-    if (!out) return BMH_OK;
-    if (total > cap) fail(BMH_ERANGE, "decompress: output capacity too small");
+    if (!verify) {
+        if (!out) return;
+        if (total > cap) fail(BMH_ERANGE, "decompress: output capacity too small");
+    }
+    std::vector<uint32_t> got;
     // batches of consecutive records: output < 1 GiB (BMH_OPT_MAX_BATCH), <= 65535 records
     const uint64_t cap_batch = max_batch_bytes(c);
     uint64_t done = 0;
@@ -1349,11 +1410,47 @@ bmh_status bmh_decompress_dev(bmh_ctx *c, const uint8_t *in, uint64_t len, uint8
             offs[k - i + 1] = offs[k - i] + rl[k];
         }
         decode_blocks(c, d_in, offs.data(), (uint32_t)(j - i), d_o, nout, oo.data());
-        BMH_HIP(hipMemcpyAsync(out + done, d_o, nout, hipMemcpyDeviceToHost, c->stream));
-        c->sync();
+        if (!want.empty()) {  // the CRC-32 of every decoded block, on the device
+            got.resize(j - i);
+            uint32_t *d_crc = (uint32_t *)c->get(WS_CRC_OUT, (j - i) * 4);
+            crc32_batch(c, d_o, make_batch(oo.data(), (uint32_t)(j - i)), d_crc);
+            c->d2h(got.data(), d_crc, (j - i) * 4);
+        }
+        try {
+            if (!verify) BMH_HIP(hipMemcpyAsync(out + done, d_o, nout, hipMemcpyDeviceToHost, c->stream));
+            c->sync();
+        } catch (...) {
+            c->deferred.clear();  // `got` goes with this call: no later sync may write it
+            throw;
+        }
+        for (size_t k = i; k < j && !want.empty(); ++k)
+            if (got[k - i] != want[k]) {
+                if (bad) *bad = k;
+                fail_crc(k, want[k], got[k - i]);
+            }
         done += nout;
         i = j;
     }
+}
+
+bmh_status bmh_decompress_dev(bmh_ctx *c, const uint8_t *in, uint64_t len, uint8_t *out, uint64_t cap, uint64_t *n_out)
+{
+    API_BEGIN
+    use_device(c);
+    if (!in || !n_out) fail(BMH_EINVAL, "null argument");
+    decompress_dev(c, in, len, out, cap, n_out, false, nullptr);
+    API_END
+}
+
+bmh_status bmh_verify_dev(bmh_ctx *c, const uint8_t *in, uint64_t len, uint64_t *n_out, uint64_t *bad_block)
+{
+    if (bad_block) *bad_block = UINT64_MAX;
+    API_BEGIN
+    use_device(c);
+    if (!in) fail(BMH_EINVAL, "null argument");
+    uint64_t n = 0;
+    decompress_dev(c, in, len, nullptr, 0, &n, true, bad_block);
+    if (n_out) *n_out = n;
     API_END
 }
 
@@ -1366,6 +1463,7 @@ bmh_status bmh_record_to_mtf(const uint8_t *rec, uint64_t len, uint8_t *mtf, uin
 }
 
 int bmh_is_container(const uint8_t *in, uint64_t len) { return in && is_container(in, len) ? 1 : 0; }
+int bmh_container_version(const uint8_t *in, uint64_t len) { return in ? container_version(in, len) : 0; }
 
 bmh_status bmh_container_info(const uint8_t *in, uint64_t len, uint64_t *nblocks, uint64_t *total_n)
 {
@@ -1381,13 +1479,28 @@ bmh_status bmh_container_record(const uint8_t *in, uint64_t len, uint64_t b, con
     API_BEGIN
     if (!in || !is_container(in, len) || len < 32) fail(BMH_ECORRUPT, "not a BMH container");
     const uint64_t nb = get_u64(in + 16);
+    const int version = container_version(in, len);
+    if (version == 2 && (nb == 0 || nb > (len - 32) / 12)) fail(BMH_ECORRUPT, "container: bad block count");
     if (b >= nb || nb > (len - 32) / 8) fail(BMH_EINVAL, "block index out of range");
-    uint64_t o = 32 + 8 * nb;
+    uint64_t o = container_table_bytes(version, nb);
     for (uint64_t k = 0; k < b; ++k) o += get_u64(in + 32 + 8 * k);
     const uint64_t l = get_u64(in + 32 + 8 * b);
     if (o > len || l > len - o) fail(BMH_ECORRUPT, "container: record overruns input");
     if (rec) *rec = in + o;
     if (rec_len) *rec_len = l;
+    API_END
+}
+
+bmh_status bmh_container_crc32(const uint8_t *in, uint64_t len, uint64_t b, uint32_t *crc)
+{
+    API_BEGIN
+    if (!in || !is_container(in, len) || len < 32) fail(BMH_ECORRUPT, "not a BMH container");
+    if (container_version(in, len) != 2) fail(BMH_EINVAL, "container: version 1 stores no checksums");
+    const uint64_t nb = get_u64(in + 16);
+    if (nb == 0 || nb > (len - 32) / 12) fail(BMH_ECORRUPT, "container: bad block count");
+    if (b >= nb) fail(BMH_EINVAL, "block index out of range");
+    const uint8_t *p = in + 32 + 8 * nb + 4 * b;
+    if (crc) *crc = (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
     API_END
 }
 
@@ -1412,6 +1525,10 @@ bmh_status bmh_ctx_set_option(bmh_ctx *c, uint32_t option, uint64_t value)
     case BMH_OPT_COPY_THREADS:
         if (value > 64) fail(BMH_ERANGE, "set_option: at most 64 copy threads");
         c->opt.copy_threads = value;
+        break;
+    case BMH_OPT_CHECKSUM:
+        if (value > 1) fail(BMH_ERANGE, "set_option: checksum is 0 or 1");
+        c->opt.checksum = value;
         break;
     default: fail(BMH_EINVAL, "set_option: unknown option " + std::to_string(option));
     }

@@ -1,9 +1,11 @@
 // cli.cpp — `bmh`, the host program: a from-scratch equivalent of the reference main()
 // (main.cpp:415-457) whose three compile-time modes become subcommands:
 //
-//   bmh compress   <in> <out> [--block-size N] [--gpus G]   (-DCOMPRESS,      main.cpp:439-447)
+//   bmh compress   <in> <out> [--block-size N] [--gpus G] [--checksum]   (-DCOMPRESS,   main.cpp:439-447)
 //   bmh decompress <in> <out> [--host]                      (-DDECOMPRESS,    main.cpp:448-456)
 //   bmh full_pipeline [dir]                                 (-DFULL_PIPELINE, main.cpp:416-438)
+//   bmh test <in> [--host]     decode without writing output and check the CRC-32 of every block
+//                              (no counterpart in the reference; like `bzip2 -t`)
 //
 // Invoked through a link named bmh_compress / bmh_decompress / bmh_full_pipeline it takes the
 // reference's positional arguments directly. The compress stdout line (main.cpp:319-323,
@@ -66,7 +68,7 @@ struct Gpus {
 };
 
 // compress(): main.cpp:300-325 (metrics print order: header size first, then print_metrics)
-int do_compress(Gpus &g, const std::string &in, const std::string &outn, uint64_t bs)
+int do_compress(Gpus &g, const std::string &in, const std::string &outn, uint64_t bs, bool checksum = false)
 {
     std::vector<uint8_t> data;
     if (!read_file(in, data)) {
@@ -77,9 +79,12 @@ int do_compress(Gpus &g, const std::string &in, const std::string &outn, uint64_
         std::cerr << "bmh: empty input (the reference crashes on empty input)" << std::endl;
         return 2;
     }
-    std::vector<uint8_t> out(bmh_compress_bound(data.size(), bs));
+    std::vector<uint8_t> out(checksum ? bmh_compress_bound_checked(data.size(), bs)
+                                      : bmh_compress_bound(data.size(), bs));
     uint64_t olen = 0;
-    int st = bmh_compress_host_multi(g.ctx.data(), (uint32_t)g.ctx.size(), data.data(), data.size(), bs, out.data(),
+    int st = checksum ? bmh_ctx_set_option(g.ctx[0], BMH_OPT_CHECKSUM, 1) : BMH_OK;
+    if (st != BMH_OK) return die("compress", st);
+    st = bmh_compress_host_multi(g.ctx.data(), (uint32_t)g.ctx.size(), data.data(), data.size(), bs, out.data(),
                                      out.size(), &olen);
     if (st != BMH_OK) return die("compress", st);
     uint64_t header = 0;
@@ -87,6 +92,7 @@ int do_compress(Gpus &g, const std::string &in, const std::string &outn, uint64_
         uint64_t nb = 0;
         bmh_container_info(out.data(), olen, &nb, nullptr);
         header = 32 + 8 * nb;
+        if (bmh_container_version(out.data(), olen) == 2) header += (4 * nb + 7) / 8 * 8;  // the CRC table
         for (uint64_t b = 0; b < nb; ++b) {
             const uint8_t *r;
             uint64_t rl;
@@ -137,6 +143,32 @@ int do_decompress(bmh_ctx *ctx, const std::string &in, const std::string &outn)
     return 0;
 }
 
+// test: the decode of decompress with no output file; on the GPU (bmh_verify_dev) the plain
+// bytes never leave the device. Version-2 containers have every block's CRC-32 checked.
+int do_test(bmh_ctx *ctx, const std::string &in)
+{
+    std::vector<uint8_t> data;
+    if (!read_file(in, data)) {
+        std::cerr << "bmh: cannot read " << in << std::endl;
+        return 2;
+    }
+    uint64_t n = 0;
+    int st;
+    if (ctx) {
+        st = bmh_verify_dev(ctx, data.data(), data.size(), &n, nullptr);
+    } else {
+        st = bmh_decompress_host(data.data(), data.size(), nullptr, 0, &n);
+        std::vector<uint8_t> out(st == BMH_OK ? n : 0);
+        if (st == BMH_OK) st = bmh_decompress_host(data.data(), data.size(), out.data(), n, &n);
+    }
+    if (st != BMH_OK) return die(in, st);
+    uint64_t nb = 1;
+    if (bmh_is_container(data.data(), data.size())) bmh_container_info(data.data(), data.size(), &nb, nullptr);
+    std::cout << in << ": OK, " << nb << " blocks, "
+              << (bmh_container_version(data.data(), data.size()) == 2 ? "CRC-32 verified" : "no checksums") << std::endl;
+    return 0;
+}
+
 bool same_file(const std::string &a, const std::string &b)
 {
     std::vector<uint8_t> x, y;
@@ -164,8 +196,9 @@ int do_full_pipeline(Gpus &g, std::string dir)
 
 int usage()
 {
-    std::cerr << "usage: bmh compress <in> <out> [--block-size N] [--gpus G]\n"
+    std::cerr << "usage: bmh compress <in> <out> [--block-size N] [--gpus G] [--checksum]\n"
                  "       bmh decompress <in> <out> [--host]   (--host: the host C++ decoder instead of the GPU)\n"
+                 "       bmh test <in> [--host]   (decode without output; checks the CRC-32 of --checksum files)\n"
                  "       bmh full_pipeline [calgarycorpus_dir]\n";
     return 1;
 }
@@ -189,12 +222,13 @@ int main(int argc, char **argv)
     }
     uint64_t bs = 0;
     int gpus = 1;
-    bool host = false;
+    bool host = false, checksum = false;
     std::vector<std::string> pos;
     for (size_t i = 0; i < args.size(); ++i) {
         if (args[i] == "--block-size" && i + 1 < args.size()) bs = std::stoull(args[++i]);
         else if (args[i] == "--gpus" && i + 1 < args.size()) gpus = std::stoi(args[++i]);
         else if (args[i] == "--host") host = true;
+        else if (args[i] == "--checksum") checksum = true;
         else pos.push_back(args[i]);
     }
     if (mode == "compress" || mode == "decompress") {
@@ -207,7 +241,15 @@ int main(int argc, char **argv)
         int st = g.open(gpus);
         if (st != BMH_OK) return die("gpu", st);
         if (mode == "decompress") return do_decompress(g.ctx[0], pos[0], pos[1]);
-        return do_compress(g, pos[0], pos[1], bs);
+        return do_compress(g, pos[0], pos[1], bs, checksum);
+    }
+    if (mode == "test") {
+        if (pos.size() != 1) return usage();
+        if (host) return do_test(nullptr, pos[0]);
+        Gpus g;
+        int st = g.open(1);
+        if (st != BMH_OK) return die("gpu", st);
+        return do_test(g.ctx[0], pos[0]);
     }
     if (mode == "full_pipeline") {
         Gpus g;

@@ -5,6 +5,9 @@
 // Container (ours, for block_size < file size): "\xffBMHBLK1" | u64 block_size |
 //   u64 nblocks | u64 total_n | u64 record_len[nblocks] | verbatim records.
 //   A record's first u64 is its primary index (< n), so the 0xff-led magic cannot be one.
+// Container version 2 (BMH_OPT_CHECKSUM): "\xffBMHBLK2" | the same three u64 | u64 record_len[nblocks] |
+//   u32 crc32[nblocks] (zlib CRC-32 of each block's plain bytes) | zero padding to a multiple of
+//   8 bytes | verbatim records. Every decoder checks the CRCs.
 //
 // Decoder replaces decompress() (main.cpp:327-345): tree parse (bytes_to_tree_dfs,
 // main.cpp:198-219), Huffman decode (huffman_reverse, main.cpp:259-281 — here table-driven
@@ -18,6 +21,7 @@
 namespace bmh {
 
 const uint8_t kContainerMagic[8] = {0xff, 'B', 'M', 'H', 'B', 'L', 'K', '1'};
+const uint8_t kContainerMagic2[8] = {0xff, 'B', 'M', 'H', 'B', 'L', 'K', '2'};
 
 void put_u64(uint8_t *p, uint64_t v)
 {
@@ -28,6 +32,60 @@ uint64_t get_u64(const uint8_t *p)
     uint64_t v = 0;
     for (int i = 0; i < 8; ++i) v |= (uint64_t)p[i] << (8 * i);
     return v;
+}
+
+// CRC-32 (zlib / IEEE 802.3) on the host: slice-by-8 tables, tab[k][v] = the register after
+// byte v and k zero bytes.
+namespace {
+struct CrcTables {
+    uint32_t tab[8][256];
+    CrcTables()
+    {
+        for (uint32_t v = 0; v < 256; ++v) {
+            uint32_t c = v;
+            for (int i = 0; i < 8; ++i) c = (c >> 1) ^ ((0u - (c & 1u)) & kCrcPoly);
+            tab[0][v] = c;
+        }
+        for (int k = 1; k < 8; ++k)
+            for (uint32_t v = 0; v < 256; ++v) tab[k][v] = tab[0][tab[k - 1][v] & 0xffu] ^ (tab[k - 1][v] >> 8);
+    }
+};
+const CrcTables &crc_tables()
+{
+    static const CrcTables t;
+    return t;
+}
+}  // namespace
+
+const uint32_t *crc32_table0() { return crc_tables().tab[0]; }
+
+uint32_t crc32_host(uint32_t crc, const uint8_t *p, uint64_t n)
+{
+    const auto &t = crc_tables().tab;
+    uint32_t s = ~crc;
+    for (; n >= 8; n -= 8, p += 8) {
+        const uint32_t a = s ^ ((uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24);
+        s = t[7][a & 0xffu] ^ t[6][(a >> 8) & 0xffu] ^ t[5][(a >> 16) & 0xffu] ^ t[4][a >> 24] ^ t[3][p[4]] ^
+            t[2][p[5]] ^ t[1][p[6]] ^ t[0][p[7]];
+    }
+    for (; n; --n, ++p) s = t[0][(s ^ *p) & 0xffu] ^ (s >> 8);
+    return ~s;
+}
+
+uint32_t crc32_xpow8(uint64_t nbytes)
+{
+    uint32_t r = 0x80000000u, base = 0x00800000u;  // x^0, x^8
+    for (; nbytes; nbytes >>= 1, base = crc32_mul(base, base))
+        if (nbytes & 1u) r = crc32_mul(r, base);
+    return r;
+}
+
+void fail_crc(uint64_t block, uint32_t stored, uint32_t computed)
+{
+    char msg[128];
+    snprintf(msg, sizeof msg, "container: CRC-32 mismatch in block %llu: stored %08x, computed %08x",
+             (unsigned long long)block, stored, computed);
+    fail(BMH_ECORRUPT, msg);
 }
 
 namespace {
@@ -235,17 +293,33 @@ void decode_record(const uint8_t *rec, uint64_t len, uint8_t *out, uint64_t cap,
     bwt_inverse(Lb.data(), n, get_u64(rec), out);
 }
 
-bool is_container(const uint8_t *in, uint64_t len) { return len >= 8 && memcmp(in, kContainerMagic, 8) == 0; }
+int container_version(const uint8_t *in, uint64_t len)
+{
+    if (len < 8) return 0;
+    return memcmp(in, kContainerMagic, 8) == 0 ? 1 : memcmp(in, kContainerMagic2, 8) == 0 ? 2 : 0;
+}
+
+bool is_container(const uint8_t *in, uint64_t len) { return container_version(in, len) != 0; }
 
 ContainerView parse_container(const uint8_t *in, uint64_t len)
 {
     if (!is_container(in, len) || len < 32) fail(BMH_ECORRUPT, "container: bad magic");
     ContainerView v;
+    v.version = container_version(in, len);
     v.block_size = get_u64(in + 8);
     v.nblocks = get_u64(in + 16);
     v.total = get_u64(in + 24);
-    if (v.nblocks == 0 || v.nblocks > (len - 32) / 8) fail(BMH_ECORRUPT, "container: bad block count");
-    uint64_t o = 32 + 8 * v.nblocks;
+    if (v.nblocks == 0 || v.nblocks > (len - 32) / (v.version == 2 ? 12 : 8))
+        fail(BMH_ECORRUPT, "container: bad block count");
+    uint64_t o = container_table_bytes(v.version, v.nblocks);
+    if (v.version == 2) {
+        if (o > len) fail(BMH_ECORRUPT, "container: tables overrun input");
+        const uint8_t *c = in + 32 + 8 * v.nblocks;
+        for (uint64_t b = 0; b < v.nblocks; ++b, c += 4)
+            v.crc.push_back((uint32_t)c[0] | (uint32_t)c[1] << 8 | (uint32_t)c[2] << 16 | (uint32_t)c[3] << 24);
+        for (; c < in + o; ++c)
+            if (*c) fail(BMH_ECORRUPT, "container: non-zero padding after the CRC table");
+    }
     for (uint64_t b = 0; b < v.nblocks; ++b) {
         const uint64_t l = get_u64(in + 32 + 8 * b);
         if (l > len || o > len - l) fail(BMH_ECORRUPT, "container: record overruns input");
@@ -279,12 +353,14 @@ void decompress(const uint8_t *in, uint64_t len, uint8_t *out, uint64_t cap, uin
     std::vector<std::thread> th;
     std::vector<std::string> errs(nt);
     std::vector<bmh_status> sts(nt, BMH_OK);
+    std::vector<uint32_t> crc(v.version == 2 ? v.nblocks : 0);  // of the decoded blocks
     for (unsigned t = 0; t < nt; ++t) {
         th.emplace_back([&, t]() {
             try {
                 for (uint64_t b = t; b < v.nblocks; b += nt) {
                     uint64_t got;
                     decode_record(in + v.rec_off[b], v.rec_len[b], out + dst[b], dst[b + 1] - dst[b], &got);
+                    if (v.version == 2) crc[b] = crc32_host(0, out + dst[b], dst[b + 1] - dst[b]);
                 }
             } catch (const Error &e) {
                 sts[t] = e.status;
@@ -304,6 +380,8 @@ void decompress(const uint8_t *in, uint64_t len, uint8_t *out, uint64_t cap, uin
     for (auto &x : th) x.join();
     for (unsigned t = 0; t < nt; ++t)
         if (sts[t] != BMH_OK) fail(sts[t], errs[t]);
+    for (uint64_t b = 0; b < crc.size(); ++b)
+        if (crc[b] != v.crc[b]) fail_crc(b, v.crc[b], crc[b]);
 }
 
 }  // namespace bmh

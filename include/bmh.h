@@ -89,6 +89,17 @@ bmh_status bmh_mtf_dev(bmh_ctx *ctx, const uint8_t *d_L, const uint64_t *offs, u
 bmh_status bmh_histogram_dev(bmh_ctx *ctx, const uint8_t *d_in, const uint64_t *offs, uint32_t nblocks,
                              uint64_t *h_freq, uint64_t *h_first);
 
+/* CRC-32 of every block of a batch, computed on the GPU (no counterpart in the reference, whose
+ * record carries no checksum): the zlib / IEEE 802.3 CRC, reflected polynomial 0xEDB88320, init
+ * and final xor 0xFFFFFFFF. h_crc (host, nblocks entries) receives one value per block. Callers
+ * of bmh_encode_blocks_dev / bmh_decode_blocks_dev who keep their data in HBM compose their own
+ * integrity check with it; the host-buffer paths do so under BMH_OPT_CHECKSUM. */
+bmh_status bmh_crc32_dev(bmh_ctx *ctx, const uint8_t *d_in, const uint64_t *offs, uint32_t nblocks,
+                         uint32_t *h_crc);
+/* The same CRC on the host, with zlib's crc32() semantics: start from crc = 0; the result of one
+ * call continues over the next bytes when passed to the next call. Host-only. */
+uint32_t bmh_crc32_host(uint32_t crc, const uint8_t *p, uint64_t n);
+
 /* Replaces the tree part of huffman() (main.cpp:245-254), traverse/build_hashmap
  * (main.cpp:132-156) and tree_to_bytes (main.cpp:174-196). Host-only. Leaves are ordered by
  * first occurrence; equal frequencies break ties by the reference's heap-address order
@@ -140,7 +151,8 @@ uint64_t bmh_record_bound(uint64_t n);
 
 /* ---- host-buffer convenience (H2D + encode + D2H) ---------------------------------- */
 /* Encodes `in` (n bytes) cut into block_size blocks (block_size 0 or >= n: one block).
- * One block => exactly the reference record; several => the BMH container (bmh_container_*).
+ * One block => exactly the reference record; several => the BMH container (bmh_container_*);
+ * under BMH_OPT_CHECKSUM always a version-2 container (size it with bmh_compress_bound_checked).
  * Returns the output size in *out_len. Batches stream through H2D / encode / D2H on separate
  * streams; with page-locked `in` / `out` (bmh_host_alloc) the copies are DMA-only. */
 bmh_status bmh_compress_host(bmh_ctx *ctx, const uint8_t *in, uint64_t n, uint64_t block_size,
@@ -150,6 +162,8 @@ bmh_status bmh_compress_host(bmh_ctx *ctx, const uint8_t *in, uint64_t n, uint64
 bmh_status bmh_compress_host_multi(bmh_ctx **ctxs, uint32_t nctx, const uint8_t *in, uint64_t n,
                                    uint64_t block_size, uint8_t *out, uint64_t out_cap, uint64_t *out_len);
 uint64_t bmh_compress_bound(uint64_t n, uint64_t block_size);
+/* Capacity sufficient under BMH_OPT_CHECKSUM = 1 (a version-2 container, also for one block). */
+uint64_t bmh_compress_bound_checked(uint64_t n, uint64_t block_size);
 /* CPUs this process may use: its affinity set capped by the cgroup CPU quota. */
 uint32_t bmh_host_cpus(void);
 /* Copy threads per copy site each of nctx contexts streaming at once uses for its pageable <->
@@ -171,16 +185,33 @@ bmh_status bmh_decode_blocks_dev(bmh_ctx *ctx, const uint8_t *d_rec, const uint6
  * contract as bmh_decompress_host). */
 bmh_status bmh_decompress_dev(bmh_ctx *ctx, const uint8_t *in, uint64_t len, uint8_t *out, uint64_t cap,
                               uint64_t *n_out);
+/* bmh_decompress_dev without an output: decodes on the GPU and, for a version-2 container,
+ * checks every block's CRC-32 there; the plain bytes never leave the device. *n_out (may be
+ * NULL) receives the decoded size. *bad_block (may be NULL) receives the first block whose CRC
+ * differs, or UINT64_MAX when the failure is structural or there is none. A version-1 container
+ * or a bare record gets the structural decode only and returns BMH_OK: whether checksums were
+ * present is bmh_container_version's answer. */
+bmh_status bmh_verify_dev(bmh_ctx *ctx, const uint8_t *in, uint64_t len, uint64_t *n_out, uint64_t *bad_block);
 /* Huffman stage inverse only (huffman_reverse, main.cpp:259-281): record -> MTF stream. */
 bmh_status bmh_record_to_mtf(const uint8_t *rec, uint64_t len, uint8_t *mtf, uint64_t cap, uint64_t *n_out);
 
 /* ---- container helpers ------------------------------------------------------------ */
 /* A BMH container is: magic "\xffBMHBLK1" | u64 block_size | u64 nblocks | u64 total_n |
- * u64 record_len[nblocks] | records (each a verbatim reference record). */
+ * u64 record_len[nblocks] | records (each a verbatim reference record).
+ * Version 2 (written under BMH_OPT_CHECKSUM) is: magic "\xffBMHBLK2" | u64 block_size |
+ * u64 nblocks | u64 total_n | u64 record_len[nblocks] | u32 crc32[nblocks] (little-endian, the
+ * CRC-32 of each block's plain bytes) | zero padding to a multiple of 8 bytes | the same records.
+ * Every decode path checks the CRCs: a mismatch is BMH_ECORRUPT, bmh_last_error() names the
+ * first bad block and both values, and the output buffer's contents are unspecified. The
+ * helpers below accept both versions. */
 int bmh_is_container(const uint8_t *in, uint64_t len);
+/* 0: not a container (e.g. a bare record); 1 or 2: the container's version. */
+int bmh_container_version(const uint8_t *in, uint64_t len);
 bmh_status bmh_container_info(const uint8_t *in, uint64_t len, uint64_t *nblocks, uint64_t *total_n);
 /* Pointer/length of record b inside a container. */
 bmh_status bmh_container_record(const uint8_t *in, uint64_t len, uint64_t b, const uint8_t **rec, uint64_t *rec_len);
+/* Stored CRC-32 of block b of a version-2 container; BMH_EINVAL on a version-1 container. */
+bmh_status bmh_container_crc32(const uint8_t *in, uint64_t len, uint64_t b, uint32_t *crc);
 
 /* ---- tuning options ---------------------------------------------------------------- */
 /* Per-context overrides of the library's own rules (not part of the reference interface; the
@@ -195,8 +226,13 @@ enum {
     BMH_OPT_ONE_PIPELINE = 6, /* 1: run each device batch on one pipeline AFTER the library's own
                                * decisions (the dense-batch census and its speculative list round
                                * still apply), so a one-stream timing pass runs the default path */
-    BMH_OPT_COPY_THREADS = 7  /* host-buffer paths: copy threads per copy site, 1..64 (default:
+    BMH_OPT_COPY_THREADS = 7, /* host-buffer paths: copy threads per copy site, 1..64 (default:
                                * bmh_copy_threads(contexts streaming at once, 0)) */
+    BMH_OPT_CHECKSUM = 8      /* 1: bmh_compress_host / bmh_compress_host_multi compute the CRC-32 of
+                               * every block's plain bytes on the GPU and always write a version-2
+                               * container, even for one block (in _multi the option of ctxs[0]
+                               * decides). The one option that changes the output: the records
+                               * inside stay the verbatim reference records. */
 };
 bmh_status bmh_ctx_set_option(bmh_ctx *ctx, uint32_t option, uint64_t value);
 
