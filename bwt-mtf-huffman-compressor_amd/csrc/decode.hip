@@ -104,7 +104,11 @@ __device__ __forceinline__ void load_dec_lds(DecLds &d, const DecTable *__restri
     }
 }
 
-// MSB-first bit window over a payload: win holds the next `valid` (>= 32 after refill) bits.
+// MSB-first bit window over a payload: win holds the next `valid` bits, >= 32 after refill()
+// and no more than that is promised, so it serves blocks whose longest code is <= kWinCode bits
+// (a longer code would be walked into bits the window does not hold yet, and consume() of more
+// than `valid` bits would wrap the count). Longer codes are read through BitSeek.
+constexpr uint32_t kWinCode = 32;
 struct BitWin {
     const uint32_t *p;  // next aligned dword to load
     const uint32_t *pend;  // first dword past the payload
@@ -136,8 +140,28 @@ struct BitWin {
     }
 };
 
-// one symbol from the window (codes up to 32 + 12 bits wide are decoded from the window;
-// the window always holds >= 32 bits here)
+// The bit source of blocks with codes of kWinCode + 1 .. 64 bits (hand-built or hostile trees:
+// huffman() needs ~2^33 symbols for a 33-bit code): the 64 bits at the read position are
+// fetched again for every symbol (bits64, as the fix-up and offset-map kernels do).
+struct BitSeek {
+    const uint8_t *pay;
+    uint64_t pay_bits, pos, win;
+    __device__ __forceinline__ void init(const uint8_t *pay_, uint64_t pay_bits_, uint64_t pos_)
+    {
+        pay = pay_;
+        pay_bits = pay_bits_;
+        pos = pos_;
+    }
+    __device__ __forceinline__ void refill() { win = bits64(pay, pay_bits, pos); }
+    __device__ __forceinline__ void consume(uint32_t n) { pos += n; }
+};
+
+template <bool WIDE> struct BitSrc { typedef BitWin type; };
+template <> struct BitSrc<true> { typedef BitSeek type; };
+
+// one symbol from the 64 bits w that start at the read position: a LUT hit within kDecLutBits,
+// else a walk down the tree, over as many bits of w as the code is long (up to 64). The caller's
+// bit source must hold that many: BitWin for codes <= kWinCode bits, BitSeek beyond.
 __device__ __forceinline__ uint32_t dec_sym_lds(const DecLds &d, uint64_t w, uint32_t &sym)
 {
     const uint32_t e = d.lut[w >> (64 - kDecLutBits)];
@@ -156,6 +180,9 @@ __device__ __forceinline__ uint32_t dec_sym_lds(const DecLds &d, uint64_t w, uin
     return k;
 }
 
+// WIDE = false serves the blocks whose codes fit the window, WIDE = true (launched only when a
+// batch has one) the blocks with longer codes; a workgroup of the other kind leaves at once.
+template <bool WIDE>
 __global__ __launch_bounds__(256) void k_hd_pass1(const DBlock *__restrict__ blks, const DecTable *__restrict__ tabs,
                                                   const uint32_t *__restrict__ seg_block, uint32_t nseg_total,
                                                   uint64_t *__restrict__ seg_end, uint32_t *__restrict__ seg_cnt,
@@ -164,6 +191,7 @@ __global__ __launch_bounds__(256) void k_hd_pass1(const DBlock *__restrict__ blk
     __shared__ DecLds d;
     const uint32_t g = blockIdx.x * 256 + threadIdx.x;
     const uint32_t bw = seg_block[blockIdx.x * 256];  // the workgroup's block
+    if ((tabs[bw].maxlen > kWinCode) != WIDE) return;
     load_dec_lds(d, &tabs[bw]);
     __syncthreads();
     if (g >= nseg_total || seg_block[g] == kNil) return;
@@ -173,7 +201,7 @@ __global__ __launch_bounds__(256) void k_hd_pass1(const DBlock *__restrict__ blk
     uint64_t pos = s0;
     uint32_t cnt = 0;
     uint16_t *bb = bnd + (size_t)g * kSyncBnd;
-    BitWin r;
+    typename BitSrc<WIDE>::type r;
     r.init(B.pay, B.pay_bits, pos);
     while (pos < stop) {
         if (cnt < kSyncBnd) bb[cnt] = (uint16_t)(pos - s0);
@@ -332,6 +360,7 @@ __global__ __launch_bounds__(256) void k_hd_scan(const DBlock *__restrict__ blks
     }
 }
 
+template <bool WIDE>  // as k_hd_pass1
 __global__ __launch_bounds__(256) void k_hd_pass3(const DBlock *__restrict__ blks, const DecTable *__restrict__ tabs,
                                                   const uint32_t *__restrict__ seg_block, uint32_t nseg_total,
                                                   const uint64_t *__restrict__ seg_start,
@@ -341,6 +370,7 @@ __global__ __launch_bounds__(256) void k_hd_pass3(const DBlock *__restrict__ blk
     __shared__ DecLds d;
     const uint32_t g = blockIdx.x * 256 + threadIdx.x;
     const uint32_t bw = seg_block[blockIdx.x * 256];
+    if ((tabs[bw].maxlen > kWinCode) != WIDE) return;
     load_dec_lds(d, &tabs[bw]);
     __syncthreads();
     if (g >= nseg_total || seg_block[g] == kNil) return;
@@ -350,7 +380,7 @@ __global__ __launch_bounds__(256) void k_hd_pass3(const DBlock *__restrict__ blk
     uint64_t pos = seg_start[g];
     uint32_t i = seg_first[g];
     uint8_t *o = mtf + B.out_off;
-    BitWin r;
+    typename BitSrc<WIDE>::type r;
     r.init(B.pay, B.pay_bits, pos);
     // symbols are written four at a time once the output address is word-aligned
     uint32_t acc = 0, na = 0;
@@ -943,7 +973,8 @@ void decode_blocks(Ctx *c, const uint8_t *d_rec, const uint64_t *rec_offs, uint3
             fail(BMH_ECORRUPT, "record " + std::to_string(b) + ": bad tree length");
         if (prim >= n) fail(BMH_ECORRUPT, "record " + std::to_string(b) + ": primary index out of range");
         build_dec_table(h + kRecordHeader, tlen, &tabs[b]);
-        // n < 2^32 bounds a Huffman tree's depth far below 64 (Fibonacci growth of the weights)
+        // n < 2^32 bounds a Huffman tree's depth far below 64 (Fibonacci growth of the weights);
+        // a record may carry any prefix code, and the kernels read codes of up to 64 bits
         if (tabs[b].maxlen > 64) fail(BMH_ECORRUPT, "record " + std::to_string(b) + ": code longer than 64 bits");
         DBlock &B = hb[b];
         B.pay = d_rec + rec_offs[b] + kRecordHeader + tlen;
@@ -1004,8 +1035,13 @@ void decode_blocks(Ctx *c, const uint8_t *d_rec, const uint64_t *rec_offs, uint3
         uint64_t *d_start = (uint64_t *)c->get(WS_SA2, (size_t)nseg * 8 + 64);
         uint32_t *d_cnt = (uint32_t *)c->get(WS_OFFS, (size_t)nseg * 4 + 64);
         uint16_t *d_bnd = (uint16_t *)c->get(WS_CHIST, (size_t)nseg * kSyncBnd * 2 + 64);
-        BMH_LAUNCH(c, "dec_huff_pass1", k_hd_pass1, cdiv(nseg, 256), 256, 0, d_blk, d_tab, d_seg_block, nseg, d_end,
-                   d_cnt, d_bnd);
+        bool wide = false;  // a block with codes longer than the bit window holds
+        for (uint32_t b = 0; b < nb; ++b) wide |= hb[b].nseg && tabs[b].maxlen > kWinCode;
+        BMH_LAUNCH(c, "dec_huff_pass1", k_hd_pass1<false>, cdiv(nseg, 256), 256, 0, d_blk, d_tab, d_seg_block, nseg,
+                   d_end, d_cnt, d_bnd);
+        if (wide)
+            BMH_LAUNCH(c, "dec_huff_pass1_wide", k_hd_pass1<true>, cdiv(nseg, 256), 256, 0, d_blk, d_tab, d_seg_block,
+                       nseg, d_end, d_cnt, d_bnd);
         // pass-1 starts are the nominal segment starts
         std::vector<uint64_t> st0(nseg, 0);
         for (uint32_t b = 0; b < nb; ++b)
@@ -1037,8 +1073,11 @@ void decode_blocks(Ctx *c, const uint8_t *d_rec, const uint64_t *rec_offs, uint3
             BMH_LAUNCH(c, "dec_huff_chain", k_hd_chain, nb, 64, 0, d_blk, P, d_map, d_start, d_cnt, d_status);
         }
         BMH_LAUNCH(c, "dec_huff_scan", k_hd_scan, nb, 256, 0, d_blk, d_cnt);
-        BMH_LAUNCH(c, "dec_huff_pass3", k_hd_pass3, cdiv(nseg, 256), 256, 0, d_blk, d_tab, d_seg_block, nseg, d_start,
-                   d_cnt, d_mtf, d_status);
+        BMH_LAUNCH(c, "dec_huff_pass3", k_hd_pass3<false>, cdiv(nseg, 256), 256, 0, d_blk, d_tab, d_seg_block, nseg,
+                   d_start, d_cnt, d_mtf, d_status);
+        if (wide)
+            BMH_LAUNCH(c, "dec_huff_pass3_wide", k_hd_pass3<true>, cdiv(nseg, 256), 256, 0, d_blk, d_tab, d_seg_block,
+                       nseg, d_start, d_cnt, d_mtf, d_status);
     }
 
     // ---- MTF^-1 -> d_L
