@@ -75,6 +75,7 @@ _SIGS = {
     "bmh_payload_bytes": (U64, [C.POINTER(CodeTable), PU64]),
     "bmh_pack_dev": (C.c_int, [P, P, PU64, U32, C.POINTER(CodeTable), P, U64, PU64, PU64]),
     "bmh_encode_blocks_dev": (C.c_int, [P, P, PU64, U32, P, U64, PU64]),
+    "bmh_codebook_dev": (C.c_int, [P, PU64, PU64, PU64, PU64, U32, C.POINTER(CodeTable), P, U64, PU64]),
     "bmh_record_bound": (U64, [U64]),
     "bmh_encode_pipelines": (U32, [P, U64, U32]),
     "bmh_ctx_last_pipelines": (U32, [P]),
@@ -322,6 +323,24 @@ class Context:
         _check(lib().bmh_encode_blocks_dev(self.h, _dp(d_in), _u64p(offs), len(offs) - 1, _dp(d_out), out_cap,
                                            _u64p(ro)), "encode_blocks")
         return ro
+
+    def codebook_dev(self, freq, first, primary, offs: np.ndarray, d_out=None, out_cap: int = 0):
+        """The encode's code-book kernels alone (bmh_codebook_dev) on caller-supplied histograms:
+        freq / first of shape (nblocks, 256), primary (nblocks). Returns (tables, rec_offs): a
+        ctypes array of nblocks CodeTable filled from the device's results and the nblocks+1
+        record offsets. With d_out, every record's header is written at its offset."""
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        nb = len(offs) - 1
+        f = np.ascontiguousarray(freq, dtype=np.uint64).reshape(-1)
+        fi = np.ascontiguousarray(first, dtype=np.uint64).reshape(-1)
+        pr = np.ascontiguousarray(primary, dtype=np.uint64).reshape(-1)
+        if f.size != nb * 256 or fi.size != nb * 256 or pr.size != nb:
+            raise BmhError(BMH_EINVAL, "codebook_dev: freq / first / primary do not match the block count")
+        tabs = (CodeTable * max(nb, 1))()
+        ro = np.zeros(nb + 1, dtype=np.uint64)
+        _check(lib().bmh_codebook_dev(self.h, _u64p(f), _u64p(fi), _u64p(pr), _u64p(offs), nb, tabs,
+                                      None if d_out is None else _dp(d_out), out_cap, _u64p(ro)), "codebook")
+        return tabs, ro
 
     def crc32_dev(self, d_in, offs: np.ndarray) -> np.ndarray:
         """CRC-32 (zlib's) of every block of a batch in device memory, computed on the GPU."""

@@ -261,6 +261,9 @@ struct OffsetChain {
 void codebook_batch(Ctx *c, const Batch &bt, const uint64_t *d_boffs, const uint32_t *d_freq, const uint32_t *d_first,
                     const uint32_t *d_prim, DevTable *d_tabs, uint64_t *d_roffs, uint64_t *d_pay_offs,
                     uint8_t *d_out, uint64_t out_cap, uint32_t *d_status, OffsetChain *chain, int sub);
+// headers staged per block by codebook_batch: 24 header bytes + <= 320 tree bytes, 16-aligned
+constexpr uint32_t kHdrStride = 352;
+void codebook_staged_headers(Ctx *c, uint32_t nb, uint8_t *hdr, uint32_t *hdr_len);  // nb * kHdrStride bytes, nb lengths
 void pack_batch_dev(Ctx *c, const uint8_t *d_mtf, const Batch &bt, const DevTable *d_tabs, const uint64_t *d_pay_offs,
                     uint8_t *d_out, const uint32_t *d_status, const uint16_t *d_chist);
 void histogram_batch(Ctx *c, const uint8_t *d_in, const Batch &bt, uint32_t *h_freq32, uint32_t *h_first32);

@@ -262,6 +262,116 @@ static void encode_blocks_one_(Ctx *c, const uint8_t *d_in, const Batch &bt, uin
     if (st & kStatusPrimary) fail(BMH_EHIP, "bwt: internal error (primary index not produced)");
 }
 
+// bmh_codebook_dev: the code-book stage of encode_blocks_one_ alone, on histograms the caller
+// supplies (checked here: the kernels trust what the MTF stage hands them). It uses the encode's
+// own workspace slots and keeps their tags as the encode does, so either may follow the other
+// with the same layout on this context.
+static void codebook_stage(Ctx *c, const uint64_t *h_freq, const uint64_t *h_first, const uint64_t *h_primary,
+                           const Batch &bt, bmh_code_table *h_tables, uint8_t *d_out, uint64_t out_cap,
+                           uint64_t *rec_offs)
+{
+    const uint32_t nb = bt.nblocks;
+    std::vector<uint32_t> f32((size_t)nb * 256, 0u), fi32((size_t)nb * 256, 0xffffffffu), p32(nb);
+    std::vector<uint64_t> seen;
+    for (uint32_t b = 0; b < nb; ++b) {
+        const uint64_t n = bt.offs[b + 1] - bt.offs[b];
+        const std::string blk = "codebook: block " + std::to_string(b);
+        if (h_primary[b] >= n) fail(BMH_EINVAL, blk + ": primary index outside the block");
+        uint64_t sum = 0;
+        seen.clear();
+        for (size_t i = (size_t)b * 256; i < (size_t)(b + 1) * 256; ++i) {
+            const uint64_t fq = h_freq[i];
+            if (!fq) continue;
+            if (fq > n - sum) fail(BMH_EINVAL, blk + ": frequencies sum past the block size");
+            sum += fq;
+            if (h_first[i] >= n) fail(BMH_EINVAL, blk + ": first occurrence outside the block");
+            seen.push_back(h_first[i]);
+            f32[i] = (uint32_t)fq;
+            fi32[i] = (uint32_t)h_first[i];
+        }
+        if (sum != n)
+            fail(BMH_EINVAL, blk + (sum ? ": frequencies sum below the block size"
+                                        : ": empty histogram (the reference segfaults on empty input)"));
+        std::sort(seen.begin(), seen.end());
+        if (std::adjacent_find(seen.begin(), seen.end()) != seen.end())
+            fail(BMH_EINVAL, blk + ": two symbols share a first occurrence");
+        p32[b] = (uint32_t)h_primary[b];
+    }
+    uint32_t *d_prim = (uint32_t *)c->get(WS_PRIMARY, nb * 4 + 64);
+    uint32_t *d_freq = (uint32_t *)c->get(WS_FREQ, (size_t)nb * 256 * 4);
+    uint32_t *d_first = (uint32_t *)c->get(WS_FIRST, (size_t)nb * 256 * 4);
+    DevTable *d_tabs = (DevTable *)c->get(WS_TABLES, nb * sizeof(DevTable));
+    uint64_t *d_roffs = (uint64_t *)c->get(WS_ROFFS, (size_t)(2 * nb + 2) * 8 + 64);
+    uint64_t *d_pay_offs = d_roffs + nb + 2;
+    uint8_t *d_misc = (uint8_t *)c->get(WS_STATUS, (size_t)(nb + 1) * 8 + 64);
+    uint32_t *d_status = (uint32_t *)d_misc;
+    uint64_t *d_boffs = (uint64_t *)(d_misc + 64);
+    const uint64_t sig = layout_sig(7, bt.offs, 0);  // as encode_blocks_one_
+    if (c->ws_tag[WS_STATUS] != sig) {
+        BMH_HIP(hipMemsetAsync(d_status, 0, 4, c->stream));
+        c->h2d(d_boffs, bt.offs.data(), (nb + 1) * 8);
+        c->ws_tag[WS_STATUS] = sig;
+    }
+    try {
+        c->h2d(d_prim, p32.data(), (size_t)nb * 4);
+        c->h2d(d_freq, f32.data(), f32.size() * 4);
+        c->h2d(d_first, fi32.data(), fi32.size() * 4);
+        // without an output buffer nothing is written past the workspaces, and no capacity binds
+        codebook_batch(c, bt, d_boffs, d_freq, d_first, d_prim, d_tabs, d_roffs, d_pay_offs, d_out,
+                       d_out ? out_cap : UINT64_MAX, d_status, nullptr, 0);
+        std::vector<uint64_t> ro(nb + 2);
+        std::vector<DevTable> tabs(nb);
+        std::vector<uint8_t> hdr((size_t)nb * kHdrStride);
+        std::vector<uint32_t> hlen(nb);
+        try {
+            c->d2h(ro.data(), d_roffs, (nb + 2) * 8);
+            c->d2h(tabs.data(), d_tabs, nb * sizeof(DevTable));
+            codebook_staged_headers(c, nb, hdr.data(), hlen.data());
+            c->sync();
+        } catch (...) {
+            c->deferred.clear();  // the vectors go with this call: no later sync may write them
+            throw;
+        }
+        const uint32_t st = (uint32_t)ro[nb + 1];
+        if (st) {  // keep the status word zero for the next batch
+            BMH_HIP(hipMemsetAsync(d_status, 0, 4, c->stream));
+            c->sync();
+        }
+        if (st & kStatusCapacity) fail(BMH_ERANGE, "codebook: output capacity too small");
+        if (st & kStatusEmpty) fail(BMH_EINVAL, "huffman: empty histogram (the reference segfaults on empty input)");
+        if (st & kStatusCodeLen) fail(BMH_ERANGE, "huffman: code longer than 64 bits");
+        if (st & kStatusPrimary) fail(BMH_EHIP, "codebook: internal error (primary index not read)");
+        memcpy(rec_offs, ro.data(), (nb + 1) * 8);
+        for (uint32_t b = 0; b < nb; ++b) {
+            bmh_code_table &t = h_tables[b];
+            memset(&t, 0, sizeof(t));
+            memcpy(t.code, tabs[b].code, sizeof(t.code));
+            memcpy(t.len, tabs[b].len, sizeof(t.len));
+            const uint8_t *h = hdr.data() + (size_t)b * kHdrStride;
+            if (hlen[b] < kRecordHeader || hlen[b] > kRecordHeader + sizeof(t.tree))
+                fail(BMH_EHIP, "codebook: internal error (header length of block " + std::to_string(b) + ")");
+            t.tree_len = hlen[b] - (uint32_t)kRecordHeader;
+            memcpy(t.tree, h + kRecordHeader, t.tree_len);
+            // leaves as the device's tree bytes spell them: preorder, an internal node is a 1 bit,
+            // a leaf a 0 bit and its 8 value bits (tree_to_bytes, main.cpp:174-196)
+            uint32_t open = 1;
+            for (uint32_t bit = 0; open && bit < 8 * t.tree_len;) {
+                if (t.tree[bit >> 3] >> (7 - (bit & 7)) & 1) {
+                    ++open;
+                    ++bit;
+                } else {
+                    --open;
+                    ++t.leaves;
+                    bit += 9;
+                }
+            }
+        }
+    } catch (...) {
+        c->ws_tag[WS_STATUS] = 0;  // a status bit may be left set on the device (encode_blocks_one)
+        throw;
+    }
+}
+
 // Streams and hardware queues: the device exposes 4 hardware queues per process
 // (GPU_MAX_HW_QUEUES); HIP gives each of the first 4 streams its own and makes later ones share
 // the least-used queue, and a stream that shares a queue serialises with the other's work. So a
@@ -1213,6 +1323,18 @@ bmh_status bmh_encode_blocks_dev(bmh_ctx *c, const uint8_t *d_in, const uint64_t
     if (!d_in || !d_out || !h_rec_offs) fail(BMH_EINVAL, "null argument");
     Batch bt = make_batch(offs, nblocks);
     encode_blocks(c, d_in, bt, d_out, out_cap, h_rec_offs, 16);
+    API_END
+}
+
+bmh_status bmh_codebook_dev(bmh_ctx *c, const uint64_t *h_freq, const uint64_t *h_first, const uint64_t *h_primary,
+                            const uint64_t *offs, uint32_t nblocks, bmh_code_table *h_tables, uint8_t *d_out,
+                            uint64_t out_cap, uint64_t *h_rec_offs)
+{
+    API_BEGIN
+    use_device(c);
+    if (!h_freq || !h_first || !h_primary || !h_tables || !h_rec_offs) fail(BMH_EINVAL, "null argument");
+    Batch bt = make_batch(offs, nblocks);
+    codebook_stage(c, h_freq, h_first, h_primary, bt, h_tables, d_out, out_cap, h_rec_offs);
     API_END
 }
 

@@ -24,8 +24,6 @@ namespace bmh {
 
 namespace {
 
-constexpr uint32_t kHdrStride = 352;  // 24 header bytes + <= 320 tree bytes, 16-aligned
-
 // Phase timing (experiment builds only, -DBMH_PROF_HUFF): lane 0 of each block's wave stores its
 // s_memtime ticks per phase of k_huff_build; codebook_batch prints the means after the launch.
 #ifdef BMH_PROF_HUFF
@@ -586,9 +584,10 @@ void codebook_batch(Ctx *c, const Batch &bt, const uint64_t *d_boffs, const uint
         BMH_HIP(hipStreamWaitEvent(c->stream, chain->ev[sub - 1], 0));
         d_base = chain->d_end[sub - 1];
     }
+    // (d_out null: bmh_codebook_dev asked for tables and offsets only, no header is copied)
     const bool fused = nb <= kRecHdrFused;
     BMH_LAUNCH(c, "rec_offs", k_rec_offs, 1, 1024, 0, nb, d_hlen, d_payb, d_roffs, d_pay_offs, out_cap, d_status, d_base,
-               fused ? d_hdr : nullptr, d_out);
+               fused && d_out ? d_hdr : nullptr, d_out);
     if (chain) {
         BMH_HIP(hipEventRecord(chain->ev[sub], c->stream));
         {
@@ -598,7 +597,18 @@ void codebook_batch(Ctx *c, const Batch &bt, const uint64_t *d_boffs, const uint
         }
         chain->cv.notify_all();
     }
-    if (!fused) BMH_LAUNCH(c, "rec_headers", k_rec_headers, nb, 64, 0, d_hdr, d_hlen, d_roffs, d_out, d_status);
+    if (!fused && d_out) BMH_LAUNCH(c, "rec_headers", k_rec_headers, nb, 64, 0, d_hdr, d_hlen, d_roffs, d_out, d_status);
+}
+
+// bmh_codebook_dev: the headers codebook_batch staged for its last batch of nb blocks on this
+// context (block b's [primary | n | tree_len | tree] at hdr + b * stride) and their lengths,
+// copied to the host; valid after the next sync().
+void codebook_staged_headers(Ctx *c, uint32_t nb, uint8_t *hdr, uint32_t *hdr_len)
+{
+    const uint8_t *d_hdr = (const uint8_t *)c->get(WS_HDR, (size_t)nb * kHdrStride + (size_t)nb * 12 + 64);
+    const uint32_t *d_hlen = (const uint32_t *)(d_hdr + (size_t)nb * kHdrStride + (size_t)nb * 8);
+    c->d2h(hdr, d_hdr, (size_t)nb * kHdrStride);
+    c->d2h(hdr_len, d_hlen, (size_t)nb * 4);
 }
 
 }  // namespace bmh

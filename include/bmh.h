@@ -131,6 +131,25 @@ bmh_status bmh_pack_dev(bmh_ctx *ctx, const uint8_t *d_mtf, const uint64_t *offs
                         const bmh_code_table *tables, uint8_t *d_out, uint64_t out_cap, const uint64_t *pay_offs,
                         uint64_t *out_bytes);
 
+/* The code-book stage of bmh_encode_blocks_dev on its own: the tree part of huffman()
+ * (main.cpp:245-254), traverse/build_hashmap (:132-156), tree_to_bytes (:174-196) and the record
+ * header of write_bytes (io_utilities.h:7-27), built on the GPU by the encode's own kernels from
+ * histograms the caller supplies. h_freq / h_first are nblocks*256 host arrays with the meaning
+ * bmh_mtf_dev returns (first is ignored where freq is 0), h_primary nblocks values; block b's size
+ * offs[b+1] - offs[b] is what its header carries, and below 128 KiB it selects the heap-history
+ * tie-break as in bmh_huffman_build_sized. Checked on the host, BMH_EINVAL before anything is
+ * launched: every block's frequencies sum to its size, the first occurrences of its present
+ * symbols are distinct and inside the block, and so is its primary index.
+ * h_tables (nblocks entries) receives the device's tables; h_rec_offs (nblocks+1) the record
+ * offsets, payload sizes included as in the encode. d_out non-NULL: block b's header
+ * [u64 primary][u64 n][u64 tree_len][tree] is written at d_out + h_rec_offs[b], the payload bytes
+ * behind it are left untouched, and a capacity below h_rec_offs[nblocks] is BMH_ERANGE with
+ * nothing written. d_out NULL: tables and offsets only (histograms whose records would not fit). */
+bmh_status bmh_codebook_dev(bmh_ctx *ctx, const uint64_t *h_freq, const uint64_t *h_first,
+                            const uint64_t *h_primary, const uint64_t *offs, uint32_t nblocks,
+                            bmh_code_table *h_tables, uint8_t *d_out, uint64_t out_cap,
+                            uint64_t *h_rec_offs);
+
 /* Whole encode (compress(), main.cpp:300-325, minus file I/O): one reference record per
  * block, [u64 primary][u64 n][u64 tree_len][tree][payload] (io_utilities.h:7-27), written
  * back to back at d_out. h_rec_offs (nblocks+1 entries) receives the record offsets. */
