@@ -105,6 +105,12 @@ _SIGS = {
     "bmh_verify_dev": (C.c_int, [P, P, U64, PU64, PU64]),
     "bmh_container_version": (C.c_int, [P, U64]),
     "bmh_container_crc32": (C.c_int, [P, U64, U64, C.POINTER(U32)]),
+    "bmh_compress_d2d": (C.c_int, [P, P, U64, U64, P, U64, PU64]),
+    "bmh_decompress_d2d": (C.c_int, [P, P, U64, P, U64, PU64]),
+    "bmh_verify_d2d": (C.c_int, [P, P, U64, PU64, PU64]),
+    "bmh_readv_d2d": (C.c_int, [P, P, U64, PU64, PU64, U32, P, U64, PU64, PU64]),
+    "bmh_container_block_size": (C.c_int, [P, U64, PU64]),
+    "bmh_container_locate": (C.c_int, [U64, U64, U64, U64, U64, PU64, PU64, PU64, PU64]),
 }
 
 
@@ -381,6 +387,60 @@ class Context:
             raise
         return n.value
 
+    # ---- device-resident containers (include/bmh.h): stream and plain bytes both in HBM
+    def compress_d2d(self, d_in, n: int, block_size: int, d_out, out_cap: int, checksum: bool = False) -> int:
+        """bmh_compress_d2d: the bytes compress_bytes gives, written at d_out; returns their count.
+        checksum=True sets BMH_OPT_CHECKSUM for this call only."""
+        olen = C.c_uint64()
+        if checksum:
+            self.set_option("checksum", 1)
+        try:
+            _check(lib().bmh_compress_d2d(self.h, _dp(d_in), n, block_size, _dp(d_out), out_cap, C.byref(olen)),
+                   "compress_d2d")
+        finally:
+            if checksum:
+                self.set_option("checksum", 0)
+        return olen.value
+
+    def decompress_d2d(self, d_in, length: int, d_out=None, cap: int = 0) -> int:
+        """bmh_decompress_d2d: decodes the stream at d_in into d_out (None: the size only);
+        returns the decoded size."""
+        n = C.c_uint64()
+        _check(lib().bmh_decompress_d2d(self.h, _dp(d_in), length, None if d_out is None else _dp(d_out), cap,
+                                        C.byref(n)), "decompress_d2d")
+        return n.value
+
+    def verify_d2d(self, d_in, length: int) -> int:
+        """verify() for a stream in device memory; raises with `.bad_block` as verify does."""
+        n, bad = C.c_uint64(), C.c_uint64()
+        st = lib().bmh_verify_d2d(self.h, _dp(d_in), length, C.byref(n), C.byref(bad))
+        try:
+            _check(st, "verify_d2d")
+        except BmhError as e:
+            e.bad_block = None if bad.value == 2**64 - 1 else bad.value
+            raise
+        return n.value
+
+    def readv_d2d(self, d_in, length: int, offs, counts, d_out, out_cap: int) -> np.ndarray:
+        """bmh_readv_d2d: plain bytes [offs[r], offs[r] + counts[r]) of the stream, clipped to its
+        size, back to back at d_out; returns the nranges + 1 output offsets. A BmhError carries
+        them as `.out_offs`, and `.bad_block` (None unless a covered block's CRC-32 differs)."""
+        o = np.ascontiguousarray(offs, dtype=np.uint64).reshape(-1)
+        k = np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1)
+        if o.size != k.size:
+            raise BmhError(BMH_EINVAL, "readv_d2d: offs and counts differ in length")
+        oo = np.zeros(o.size + 1, dtype=np.uint64)
+        bad = C.c_uint64()
+        st = lib().bmh_readv_d2d(self.h, _dp(d_in), length, _u64p(o), _u64p(k), o.size,
+                                 None if d_out is None else _dp(d_out), out_cap, _u64p(oo), C.byref(bad))
+        try:
+            _check(st, "readv_d2d")
+        except BmhError as e:
+            e.bad_block = None if bad.value == 2**64 - 1 else bad.value
+            e.out_offs = oo
+            raise
+        return oo
+
     def synth_splitmix64(self, d_out, nbytes: int, seed: int = 0, offset: int = 0) -> None:
         _check(lib().bmh_synth_splitmix64_dev(self.h, _dp(d_out), nbytes, seed, offset), "synth")
 
@@ -525,6 +585,23 @@ def container_crcs(data) -> list[int]:
     return out
 
 
+def container_block_size(data) -> int:
+    """The block_size field of a container's header; BmhError (BMH_EINVAL) on a bare record."""
+    a = as_u8(data)
+    v = C.c_uint64()
+    _check(lib().bmh_container_block_size(_ptr(a), a.size, C.byref(v)), "container_block_size")
+    return v.value
+
+
+def container_locate(block_size: int, nblocks: int, total_n: int, offset: int, count: int) -> tuple[int, int, int, int]:
+    """bmh_container_locate: (first_block, block_count, skip, n_read) of a pread of `count` bytes
+    at `offset`; BmhError (BMH_ECORRUPT) when the geometry breaks the container's rule."""
+    out = [C.c_uint64() for _ in range(4)]
+    _check(lib().bmh_container_locate(block_size, nblocks, total_n, offset, count, *[C.byref(x) for x in out]),
+           "container_locate")
+    return tuple(x.value for x in out)
+
+
 def crc32(data, crc: int = 0) -> int:
     """zlib.crc32 semantics (bmh_crc32_host): the CRC the version-2 container stores."""
     a = as_u8(data)
@@ -645,4 +722,4 @@ def decompress(encoded_file_name: str, decoded_file_name: str) -> None:
 __all__ = ["BmhError", "CodeTable", "Context", "DevBuf", "lib", "bwt", "move_to_front", "huffman",
            "tree_to_bytes", "compress", "decompress", "compress_bytes_multi", "decompress_bytes",
            "record_to_mtf", "huffman_build", "node_ranks", "payload_bytes", "container_records", "is_container",
-           "container_version", "container_crcs", "crc32", "metrics_line", "default_context"]
+           "container_version", "container_crcs", "container_block_size", "container_locate", "crc32", "metrics_line", "default_context"]

@@ -54,7 +54,7 @@ enum Slot : int {
     WS_MTF_R, WS_MTF_S, WS_MTF_SUPER, WS_MTF_CHUNKS, WS_FREQ, WS_FIRST, WS_PRIMARY, WS_PACK_BITS,
     WS_PACK_CHUNKS, WS_TABLES, WS_HDR, WS_HDR_OFFS, WS_IN, WS_OUT, WS_IN2, WS_OUT2, WS_IN3, WS_OUT3, WS_RESOLVED, WS_FIN_CUR, WS_FIN_NXT,
     WS_DSEG_CUR, WS_DSEG_NXT, WS_DLARGE, WS_DLARGE2, WS_DGROUPS, WS_KEY8, WS_ROFFS, WS_STATUS, WS_PACK_HIST, WS_FINT_CUR, WS_FINT_NXT, WS_FINB_CUR, WS_FINB_NXT, WS_KEY8B, WS_RUN_MISC, WS_RUN_MOVE, WS_RUN_IN, WS_RUN_L, WS_RUNS, WS_RUN_PRIM, WS_BAND, WS_SYNTH, WS_ALPHA,
-    WS_CRC_TAB, WS_CRC_BLK, WS_CRC_PART, WS_CRC_OUT, WS_COUNT_
+    WS_CRC_TAB, WS_CRC_BLK, WS_CRC_PART, WS_CRC_OUT, WS_PIECES, WS_HEADS, WS_COUNT_
 };
 
 struct Ctx {
@@ -352,6 +352,30 @@ inline uint64_t container_table_bytes(int version, uint64_t nblocks)
 }
 [[noreturn]] void fail_crc(uint64_t block, uint32_t stored, uint32_t computed);
 void decompress(const uint8_t *in, uint64_t len, uint8_t *out, uint64_t cap, uint64_t *n_out);
+// The container's geometry rule and the blocks a pread of [offset, offset + count) covers
+// (bmh_container_locate, include/bmh.h); BMH_ECORRUPT when the three numbers break the rule.
+void container_locate(uint64_t block_size, uint64_t nblocks, uint64_t total_n, uint64_t offset, uint64_t count,
+                      uint64_t *first_block, uint64_t *block_count, uint64_t *skip, uint64_t *n_read);
+
+// Device-resident containers (container.hip). capi.cpp lends them its batch encode
+// and batch limit.
+void encode_blocks(Ctx *c, const uint8_t *d_in, const Batch &bt, uint8_t *d_out, uint64_t out_cap, uint64_t *rec_offs,
+                   int max_pipes);
+uint64_t max_batch_bytes(const Ctx *c);  // BMH_OPT_MAX_BATCH
+// One copy of a gather: `len` bytes from d_src + src to d_dst + dst.
+struct Piece {
+    uint64_t src, dst, len;
+};
+// Copies every piece in one launch on the context's stream (asynchronous); the pieces' destinations
+// are disjoint from each other and from every source.
+void gather_pieces(Ctx *c, const uint8_t *d_src, uint8_t *d_dst, const std::vector<Piece> &pieces);
+void compress_d2d(Ctx *c, const uint8_t *d_in, uint64_t n, uint64_t block_size, uint8_t *d_out, uint64_t out_cap,
+                  uint64_t *out_len);
+// bmh_decompress_d2d, or with `verify` bmh_verify_d2d (decodes into the workspace; *bad as bmh_verify_dev)
+void decompress_d2d(Ctx *c, const uint8_t *d_in, uint64_t len, uint8_t *d_out, uint64_t cap, uint64_t *n_out,
+                    bool verify, uint64_t *bad);
+void readv_d2d(Ctx *c, const uint8_t *d_in, uint64_t len, const uint64_t *h_offs, const uint64_t *h_counts,
+               uint32_t nranges, uint8_t *d_out, uint64_t out_cap, uint64_t *h_out_offs, uint64_t *bad);
 
 }  // namespace bmh
 

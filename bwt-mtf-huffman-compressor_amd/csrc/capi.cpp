@@ -606,7 +606,7 @@ static uint32_t pipelines_for(Ctx *c, uint64_t total, uint32_t nb, int max_pipes
     return S <= 1 ? 1u : S;
 }
 
-static uint64_t max_batch_bytes(const Ctx *c)
+uint64_t max_batch_bytes(const Ctx *c)
 {
     const uint64_t v = c->opt.max_batch;  // BMH_OPT_MAX_BATCH
     return v ? v : (1ull << 30);
@@ -1573,6 +1573,66 @@ bmh_status bmh_verify_dev(bmh_ctx *c, const uint8_t *in, uint64_t len, uint64_t 
     uint64_t n = 0;
     decompress_dev(c, in, len, nullptr, 0, &n, true, bad_block);
     if (n_out) *n_out = n;
+    API_END
+}
+
+// ---- device-resident containers (container.hip)
+bmh_status bmh_compress_d2d(bmh_ctx *c, const uint8_t *d_in, uint64_t n, uint64_t block_size, uint8_t *d_out,
+                            uint64_t out_cap, uint64_t *out_len)
+{
+    API_BEGIN
+    use_device(c);
+    compress_d2d(c, d_in, n, block_size, d_out, out_cap, out_len);
+    API_END
+}
+
+bmh_status bmh_decompress_d2d(bmh_ctx *c, const uint8_t *d_in, uint64_t len, uint8_t *d_out, uint64_t cap,
+                              uint64_t *n_out)
+{
+    API_BEGIN
+    use_device(c);
+    if (!d_in || !n_out) fail(BMH_EINVAL, "null argument");
+    decompress_d2d(c, d_in, len, d_out, cap, n_out, false, nullptr);
+    API_END
+}
+
+bmh_status bmh_verify_d2d(bmh_ctx *c, const uint8_t *d_in, uint64_t len, uint64_t *n_out, uint64_t *bad_block)
+{
+    if (bad_block) *bad_block = UINT64_MAX;
+    API_BEGIN
+    use_device(c);
+    if (!d_in) fail(BMH_EINVAL, "null argument");
+    uint64_t n = 0;
+    decompress_d2d(c, d_in, len, nullptr, 0, &n, true, bad_block);
+    if (n_out) *n_out = n;
+    API_END
+}
+
+bmh_status bmh_readv_d2d(bmh_ctx *c, const uint8_t *d_in, uint64_t len, const uint64_t *h_offs,
+                         const uint64_t *h_counts, uint32_t nranges, uint8_t *d_out, uint64_t out_cap,
+                         uint64_t *h_out_offs, uint64_t *bad_block)
+{
+    if (bad_block) *bad_block = UINT64_MAX;
+    API_BEGIN
+    use_device(c);
+    readv_d2d(c, d_in, len, h_offs, h_counts, nranges, d_out, out_cap, h_out_offs, bad_block);
+    API_END
+}
+
+bmh_status bmh_container_block_size(const uint8_t *in, uint64_t len, uint64_t *block_size)
+{
+    API_BEGIN
+    if (!in || !is_container(in, len) || len < 32) fail(BMH_EINVAL, "not a BMH container");
+    if (block_size) *block_size = get_u64(in + 8);
+    API_END
+}
+
+bmh_status bmh_container_locate(uint64_t block_size, uint64_t nblocks, uint64_t total_n, uint64_t offset,
+                                uint64_t count, uint64_t *first_block, uint64_t *block_count, uint64_t *skip,
+                                uint64_t *n_read)
+{
+    API_BEGIN
+    container_locate(block_size, nblocks, total_n, offset, count, first_block, block_count, skip, n_read);
     API_END
 }
 

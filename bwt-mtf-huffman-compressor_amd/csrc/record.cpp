@@ -330,6 +330,24 @@ ContainerView parse_container(const uint8_t *in, uint64_t len)
     return v;
 }
 
+// Geometry rule: block b holds plain bytes [b * block_size, min((b + 1) * block_size, total_n)),
+// and nblocks == ceil(total_n / block_size). The writers always produce it; no decoder needs it,
+// but a range read finds its blocks by it.
+void container_locate(uint64_t block_size, uint64_t nblocks, uint64_t total_n, uint64_t offset, uint64_t count,
+                      uint64_t *first_block, uint64_t *block_count, uint64_t *skip, uint64_t *n_read)
+{
+    if (block_size == 0 || block_size >= 0xffffffffull) fail(BMH_ECORRUPT, "container: bad block size");
+    // ceil without forming total_n + block_size - 1, which may wrap
+    if (nblocks != total_n / block_size + (total_n % block_size != 0))
+        fail(BMH_ECORRUPT, "container: block count does not match the total and the block size");
+    const uint64_t nr = offset < total_n ? std::min(count, total_n - offset) : 0;  // (offset + count may wrap)
+    const uint64_t first = nr ? offset / block_size : 0;
+    if (first_block) *first_block = first;
+    if (block_count) *block_count = nr ? (offset + nr - 1) / block_size - first + 1 : 0;
+    if (skip) *skip = nr ? offset - first * block_size : 0;
+    if (n_read) *n_read = nr;
+}
+
 void decompress(const uint8_t *in, uint64_t len, uint8_t *out, uint64_t cap, uint64_t *n_out)
 {
     if (!is_container(in, len)) {

@@ -93,7 +93,8 @@ bmh_status bmh_histogram_dev(bmh_ctx *ctx, const uint8_t *d_in, const uint64_t *
  * record carries no checksum): the zlib / IEEE 802.3 CRC, reflected polynomial 0xEDB88320, init
  * and final xor 0xFFFFFFFF. h_crc (host, nblocks entries) receives one value per block. Callers
  * of bmh_encode_blocks_dev / bmh_decode_blocks_dev who keep their data in HBM compose their own
- * integrity check with it; the host-buffer paths do so under BMH_OPT_CHECKSUM. */
+ * integrity check with it; the host-buffer paths and the device-resident container calls
+ * (bmh_compress_d2d and its companions) do so under BMH_OPT_CHECKSUM. */
 bmh_status bmh_crc32_dev(bmh_ctx *ctx, const uint8_t *d_in, const uint64_t *offs, uint32_t nblocks,
                          uint32_t *h_crc);
 /* The same CRC on the host, with zlib's crc32() semantics: start from crc = 0; the result of one
@@ -232,6 +233,66 @@ bmh_status bmh_container_record(const uint8_t *in, uint64_t len, uint64_t b, con
 /* Stored CRC-32 of block b of a version-2 container; BMH_EINVAL on a version-1 container. */
 bmh_status bmh_container_crc32(const uint8_t *in, uint64_t len, uint64_t b, uint32_t *crc);
 
+/* The header's block_size field; BMH_EINVAL if `in` is not a container (e.g. a bare record). */
+bmh_status bmh_container_block_size(const uint8_t *in, uint64_t len, uint64_t *block_size);
+/* The geometry rule every writer above keeps and the range read below relies on: block b of a
+ * container holds plain bytes [b*block_size, min((b+1)*block_size, total_n)), and nblocks ==
+ * ceil(total_n / block_size). Pure arithmetic, host-only: BMH_ECORRUPT when the three numbers
+ * break the rule or block_size is 0 or >= 2^32 - 1. Otherwise the blocks a read of `count` bytes
+ * at `offset` covers, with pread semantics: *n_read = min(count, total_n - offset) if offset <
+ * total_n, else 0 (offset + count may exceed 2^64 - 1 and does not wrap). *n_read == 0 gives
+ * *block_count == 0 (and first_block, skip 0); otherwise *first_block = offset / block_size and
+ * *skip = offset - *first_block * block_size, the bytes of the first block before the range.
+ * Every output pointer may be NULL. */
+bmh_status bmh_container_locate(uint64_t block_size, uint64_t nblocks, uint64_t total_n, uint64_t offset,
+                                uint64_t count, uint64_t *first_block, uint64_t *block_count, uint64_t *skip,
+                                uint64_t *n_read);
+
+/* ---- device-resident containers ---------------------------------------------------- */
+/* The container as an object in HBM: written, decoded, verified and read by ranges without the
+ * plain bytes or the records crossing PCIe. Every d_* pointer is device memory of the context's
+ * device. Only O(nblocks) metadata moves between host and device: the 32-byte header, the
+ * record-length and CRC tables, the first bytes of each record (its 24-byte header) and status
+ * words. The decode paths read whole aligned 4-byte words around a record's payload, so d_in + len
+ * rounded up to a multiple of 4 must lie inside d_in's allocation (true of any hipMalloc'd block). */
+
+/* bmh_compress_host for input and output in HBM: d_out[0, *out_len) receives exactly the bytes
+ * bmh_compress_host writes for the same input, block_size and context options (one block without
+ * BMH_OPT_CHECKSUM: the bare reference record; else a version-1 container, or version 2 under
+ * BMH_OPT_CHECKSUM). Size d_out with bmh_compress_bound / bmh_compress_bound_checked. Inputs of
+ * any size go in device batches of at most BMH_OPT_MAX_BATCH bytes. BMH_EINVAL: n == 0, a null
+ * pointer, d_out not 8-byte aligned, or d_in[0, n) and d_out[0, out_cap) overlap. BMH_ERANGE:
+ * block_size >= 2^32 - 1, or out_cap too small. On every path, successful or not, no byte at or
+ * beyond d_out + out_cap is written. */
+bmh_status bmh_compress_d2d(bmh_ctx *ctx, const uint8_t *d_in, uint64_t n, uint64_t block_size,
+                            uint8_t *d_out, uint64_t out_cap, uint64_t *out_len);
+/* bmh_decompress_dev for a stream in HBM (a bare record or a container of either version, at any
+ * byte alignment), decoded straight into d_out: the same status, *n_out and bytes for the same
+ * stream, d_out == NULL size query, BMH_ERANGE on a small cap and every BMH_ECORRUPT case
+ * included. Version-2 CRCs are checked on the device. Overlapping d_in / d_out: BMH_EINVAL. */
+bmh_status bmh_decompress_d2d(bmh_ctx *ctx, const uint8_t *d_in, uint64_t len,
+                              uint8_t *d_out, uint64_t cap, uint64_t *n_out);
+/* bmh_verify_dev for a stream in HBM: same outputs, same bad_block rule. */
+bmh_status bmh_verify_d2d(bmh_ctx *ctx, const uint8_t *d_in, uint64_t len,
+                          uint64_t *n_out, uint64_t *bad_block);
+/* Vectored range read. Range r is plain bytes [h_offs[r], h_offs[r] + h_counts[r]) of the stream,
+ * clipped to its size as bmh_container_locate clips (a bare record is a one-block stream). The
+ * clipped ranges are written back to back, in the order given, range r at d_out + h_out_offs[r];
+ * h_out_offs (host, nranges + 1 entries) is filled whenever the header parses and its geometry
+ * holds. out_cap < h_out_offs[nranges]: BMH_ERANGE, nothing launched, nothing written. Ranges may
+ * overlap, repeat, come in any order and be empty.
+ * Only the blocks some range touches are decoded, each once however many ranges touch it, in
+ * batches of at most BMH_OPT_MAX_BATCH decoded bytes, into the context's workspace; one kernel
+ * launch per batch copies every (range, block) intersection to its place. For each such block the
+ * record header's n must equal the size the geometry rule gives (else BMH_ECORRUPT), and in a
+ * version-2 container its CRC-32 is checked on the device before the call returns: a mismatch is
+ * BMH_ECORRUPT, *bad_block (may be NULL) and bmh_last_error() name the block, and d_out's contents
+ * are unspecified. *bad_block is UINT64_MAX in every other case. Blocks no range touches are
+ * neither read nor checked: damage there does not fail the call. */
+bmh_status bmh_readv_d2d(bmh_ctx *ctx, const uint8_t *d_in, uint64_t len,
+                         const uint64_t *h_offs, const uint64_t *h_counts, uint32_t nranges,
+                         uint8_t *d_out, uint64_t out_cap, uint64_t *h_out_offs, uint64_t *bad_block);
+
 /* ---- tuning options ---------------------------------------------------------------- */
 /* Per-context overrides of the library's own rules (not part of the reference interface; the
  * library reads no environment variables). Value 0 restores the default. Results never depend
@@ -239,7 +300,8 @@ bmh_status bmh_container_crc32(const uint8_t *in, uint64_t len, uint64_t b, uint
 enum {
     BMH_OPT_PIPELINES = 1,    /* pipelines (streams) per device batch, 1..16 (default: the size rule) */
     BMH_OPT_STREAM_BATCH = 2, /* bmh_compress_host batch bytes (default 256 MiB) */
-    BMH_OPT_MAX_BATCH = 3,    /* largest device batch bytes of the host-buffer paths (default 1 GiB) */
+    BMH_OPT_MAX_BATCH = 3,    /* largest device batch bytes of the host-buffer and device-resident
+                               * container paths (default 1 GiB) */
     BMH_OPT_MTF_CHUNK = 4,    /* MTF chunk symbols, 64..4096 (default: adaptive) */
     BMH_OPT_CHECK_LISTS = 5,  /* 1: check every BWT list round and print its census (diagnostic, slow) */
     BMH_OPT_ONE_PIPELINE = 6, /* 1: run each device batch on one pipeline AFTER the library's own
@@ -247,7 +309,7 @@ enum {
                                * still apply), so a one-stream timing pass runs the default path */
     BMH_OPT_COPY_THREADS = 7, /* host-buffer paths: copy threads per copy site, 1..64 (default:
                                * bmh_copy_threads(contexts streaming at once, 0)) */
-    BMH_OPT_CHECKSUM = 8      /* 1: bmh_compress_host / bmh_compress_host_multi compute the CRC-32 of
+    BMH_OPT_CHECKSUM = 8      /* 1: bmh_compress_host / bmh_compress_host_multi / bmh_compress_d2d compute the CRC-32 of
                                * every block's plain bytes on the GPU and always write a version-2
                                * container, even for one block (in _multi the option of ctxs[0]
                                * decides). The one option that changes the output: the records
